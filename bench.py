@@ -24,9 +24,23 @@ slice of the caller's array), timed on its own (`path_gather`).  `--stub`
 rehearses the launcher and the timing harness on CPU ranks over gloo.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), including
-`roofline` for the dominant kernel (HIP events on the launch stream) and
+`roofline` for the dominant kernel (HIP events on the launch stream).
+
+A plain run sets up, warms up, times the K steps and prints the line.
+`--full` adds everything that takes runs of its own, after the timed region:
+the oracle check of the timed data (`check`), `path_gather`, the other
+schedules and the two halves alone (`alone_after_timing`), N2's sequential
+run, c2-host's pinned-link rates, one-chunk calls and device-entry
+comparison, and
 `cpu_baseline` (the stanc-faithful CPU oracle, libm log, timed on a bounded
-sample of the same workload on the host cores).
+sample of the same workload on the host cores).  Without it those fields are
+null or absent.
+
+`--dump-outputs DIR` writes, after the timed steps, what the last timed step
+left in the request's output arrays as DIR/<name>.npy (float64, the integer
+arrays converted exactly), at most 64 MB in all: an array that does not fit
+its share is a fixed, seeded sample of its elements (in the array's memory
+order), the same from run to run.
 """
 import argparse
 import ctypes as C
@@ -89,7 +103,17 @@ def parse():
     ap.add_argument("--stub", action="store_true",
                     help="launcher rehearsal without a GPU: CPU ranks over gloo, a fixed numpy step")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port for --gpus N > 1 (0: a free one)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run what the headline figure does not need: the oracle check, "
+                         "the path gather, the other schedules and kernels alone, the CPU baseline (each still "
+                         "switched off by its own --no-... option)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the output arrays of the last timed step as DIR/<name>.npy (float64, at most 64 MB "
+                         "in all; a fixed, seeded sample of an array that does not fit)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 # ---------------------------------------------------------------------------
@@ -233,6 +257,36 @@ def path_gather(rk, zs):
             "destination": "pinned host buffer per rank (zstar_t [T, P] int32)", "first_row_verified": ok}
 
 
+DUMP_CAP = 60_000_000  # bytes of array data per dump (the .npy headers stay well inside 64 MB)
+DUMP_SEED = 20170717
+
+
+def dump_outputs(dirname, rk, arrays):
+    """--dump-outputs: the request's output arrays (device tensors or numpy
+    arrays, as the last timed step left them) -> DIR/<name>.npy in float64.
+    Every array of every rank gets an equal share of DUMP_CAP (the cap holds
+    for DIR as a whole); one that does not fit is
+    written as a sample of its elements in memory order, at sorted indices
+    drawn from a generator seeded by DUMP_SEED and the array's position (the
+    same indices in every run with the same arguments).  Rank 0 writes
+    <name>.npy, rank r > 0 <name>.rank<r>.npy."""
+    d = pathlib.Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    share = DUMP_CAP // max(1, rk.world) // max(1, len(arrays)) // 8
+    for j, (name, arr) in enumerate(sorted(arrays.items())):
+        t = arr if torch.is_tensor(arr) else torch.from_numpy(np.ascontiguousarray(arr))
+        flat = t.reshape(-1)
+        if flat.numel() > share:
+            g = torch.Generator()
+            g.manual_seed(DUMP_SEED + j)
+            idx = torch.randint(0, flat.numel(), (share,), generator=g, dtype=torch.int64).sort().values
+            out = flat[idx.to(flat.device)]
+        else:
+            out = flat.reshape(t.shape)
+        out = out.to(torch.float64).cpu().numpy()
+        np.save(d / (f"{name}.npy" if rk.rank == 0 else f"{name}.rank{rk.rank}.npy"), out)
+
+
 def stub_workload(a, rk):
     """--stub: the launcher, rendezvous and timing harness on CPU ranks (gloo):
     each step is a fixed numpy recursion over this rank's own block."""
@@ -250,6 +304,8 @@ def stub_workload(a, rk):
         rk.all_reduce_sum(acc)
 
     elapsed, emax, per_rank = timed_region(rk, step, a.steps, a.warmup)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rk, {"acc": acc})
     if rk.rank == 0:
         print(json.dumps({"metric": "stub (launcher rehearsal)", "value": rk.world * P * T * a.steps / emax,
                           "unit": "series-timesteps/s", "n_gpus": rk.world, "steps": a.steps, "warmup": a.warmup,
@@ -502,7 +558,7 @@ def c2_workload(a, lib, rk):
     checked = []
 
     def check():
-        if not a.no_check and rank == 0:
+        if a.full and not a.no_check and rank == 0:
             checked.append(check_slice(run, x, draws, P, T))
 
     elapsed_rank, elapsed, per_rank = timed_region(rk, step, a.steps, a.warmup,
@@ -513,13 +569,15 @@ def c2_workload(a, lib, rk):
     step_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in evs]))
     rank_step_ms = [v[0] for v in rk.gather([step_ms])]
     bad = int((run.out["pair_status"] != 0).sum().item())
-    gather = None if a.no_path_gather else path_gather(rk, run.out["zstar_t"])
-    # after the timed region: the other schedules once each (untimed for `value`):
+    if a.dump_outputs:  # before anything else writes the output buffers
+        dump_outputs(a.dump_outputs, rk, run.out)
+    gather = path_gather(rk, run.out["zstar_t"]) if a.full and not a.no_path_gather else None
+    # --full, after the timed region: the other schedules once each (untimed for `value`):
     # the two halves alone (the north star's "batched forward-backward") and the
     # two-kernel schedule
     solo = {}
     others = [nm for nm in ("step", "two", "vfb", "fused", "split") if nm != name]
-    for nm in ["fb", "viterbi"] + others:
+    for nm in (["fb", "viterbi"] + others) if a.full else []:
         ts = []
         for _ in range(3):  # back to back on one stream; median of three launches
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -579,9 +637,9 @@ def c2_workload(a, lib, rk):
                                    "roofline_frac": vit_b * units / (solo["viterbi"] * 1e-3) / HBM_PEAK},
                 **{SCHEDULE_KERNELS[nm][1]: {"ms": solo[nm],
                                               "roofline_frac": whole_b * units / (solo[nm] * 1e-3) / HBM_PEAK}
-                   for nm in others if nm != "step"}},
+                   for nm in others if nm != "step"}} if a.full else None,
         }
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(T, a.cpu_seconds, a.seed)
         print(json.dumps(line), flush=True)
 
@@ -659,35 +717,40 @@ def c2_host_workload(a, lib, rk):
         if st < 0:
             raise RuntimeError(lib.hhmm_last_error().decode())
 
-    rates = link_rates(dev)
+    rates = link_rates(dev) if a.full else None  # nine 1 GiB pinned copies of their own
     fresh_t0 = time.perf_counter()
     call(0)  # first call: pinned staging and device buffers come from the library's pools after this
     first_s = time.perf_counter() - fresh_t0
     for _ in range(max(0, a.warmup - 1)):
         call(0)
     elapsed_rank, elapsed, per_rank = timed_region(rk, lambda i: call(0), a.steps, 0)
-    one_chunk = []
-    for _ in range(2):
-        t0 = time.perf_counter()
-        call(_abi.flag_host_chunks(1))
-        one_chunk.append(time.perf_counter() - t0)
-    # the same request on the device entry: bit-identical outputs
-    run = DeviceRun(lib, x_d, draws_d, P, T, dev)
-    run.launch("step")
-    torch.cuda.synchronize(dev)
-    same = {
-        "loglik": bool(np.array_equal(run.out["loglik"].cpu().numpy(), out["loglik"])),
-        "logp_zstar": bool(np.array_equal(run.out["logp_zstar"].cpu().numpy(), out["logp_zstar"])),
-        "zstar_t": bool(np.array_equal(run.out["zstar_t"].cpu().numpy(), out["zstar_t"])),
-        "gamma_tk": bool(np.array_equal(run.out["gamma_tk"].cpu().numpy(), out["gamma_tk"])),
-        "pair_status": bool(np.array_equal(run.out["pair_status"].cpu().numpy(), status)),
-    }
-    del run
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rk, dict(out, pair_status=status))
+    one_chunk, same = None, None
+    if a.full:
+        one_chunk = []
+        for _ in range(2):
+            t0 = time.perf_counter()
+            call(_abi.flag_host_chunks(1))
+            one_chunk.append(time.perf_counter() - t0)
+        # the same request on the device entry: bit-identical outputs
+        run = DeviceRun(lib, x_d, draws_d, P, T, dev)
+        run.launch("step")
+        torch.cuda.synchronize(dev)
+        same = {
+            "loglik": bool(np.array_equal(run.out["loglik"].cpu().numpy(), out["loglik"])),
+            "logp_zstar": bool(np.array_equal(run.out["logp_zstar"].cpu().numpy(), out["logp_zstar"])),
+            "zstar_t": bool(np.array_equal(run.out["zstar_t"].cpu().numpy(), out["zstar_t"])),
+            "gamma_tk": bool(np.array_equal(run.out["gamma_tk"].cpu().numpy(), out["gamma_tk"])),
+            "pair_status": bool(np.array_equal(run.out["pair_status"].cpu().numpy(), status)),
+        }
+        del run
     up = x.nbytes + sum(v.nbytes for v in draws.values())
     down = sum(v.nbytes for v in out.values()) + status.nbytes
     # each direction alone, and both together (this host link measures about
     # half-duplex: the two copies at once share one aggregate rate)
-    t_bound = max(up / rates["h2d"], down / rates["d2h"], (up + down) / (2.0 * rates["both"]))
+    t_bound = (max(up / rates["h2d"], down / rates["d2h"], (up + down) / (2.0 * rates["both"]))
+               if rates is not None else None)
     if rank == 0:
         value = world * P * T * a.steps / elapsed
         step_s = elapsed / a.steps
@@ -710,14 +773,14 @@ def c2_host_workload(a, lib, rk):
                                    "gamma_tk zstar_t loglik logp_zstar, host to host",
                        "pairs_per_gpu": P, "T": T, "parallelism": f"pairs sharded over {world} GPU(s)"},
             "host_link": {"bytes_up": up, "bytes_down": down,
-                          "pinned_GBps": {k: v / 1e9 for k, v in rates.items()},
-                          "bound_ms": t_bound * 1e3,
-                          "frac_of_link_bound": t_bound / step_s,
+                          "pinned_GBps": {k: v / 1e9 for k, v in rates.items()} if rates is not None else None,
+                          "bound_ms": t_bound * 1e3 if rates is not None else None,
+                          "frac_of_link_bound": t_bound / step_s if rates is not None else None,
                           "end_to_end_GBps": (up + down) / step_s / 1e9,
                           "bound": "max(bytes_up / pinned H2D rate, bytes_down / pinned D2H rate, (bytes_up + "
                                    "bytes_down) / the aggregate rate of both directions at once): the transfers "
                                    "overlapped, at the rates torch's pinned copies reach on this host"},
-            "one_chunk_ms": [t * 1e3 for t in one_chunk],
+            "one_chunk_ms": [t * 1e3 for t in one_chunk] if one_chunk is not None else None,
             "first_call_ms": first_s * 1e3,
             "bit_identical_to_device_entry": same,
             "library": lib.hhmm_version().decode(),
@@ -907,8 +970,10 @@ def other_workload(a, lib, rk):
     dev_ms = ev[0].elapsed_time(ev[1]) / a.steps
     units = P * T
     B = bps(T, kw["S"])
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rk, dict(w["outs"], pair_status=status))
     sequential = None
-    if a.workload == "n2" and not a.no_sequential:
+    if a.full and a.workload == "n2" and not a.no_sequential:
         # after the timed region, once: the same request on the sequential
         # state-parallel kernels (HHMM_FLAG_SCAN_OFF), what the scan replaces
         req = w["req"]
@@ -938,7 +1003,7 @@ def other_workload(a, lib, rk):
         }
         if sequential:
             line["sequential_after_timing"] = sequential
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline_grid(model, data, draws, pars, T, a.cpu_seconds, a.seed)
         print(json.dumps(line), flush=True)
 
@@ -999,6 +1064,8 @@ def features_workload(a, lib, rk):
     _, elapsed, per_rank = timed_region(rk, step, a.steps, a.warmup)
     dev_ms = ev[0].elapsed_time(ev[1]) / a.steps
     m = int(legs.n_legs)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rk, {k: v[:m] for k, v in cols.items()})
     # algorithmic bytes: price + size per tick; per leg the two index times and 52 B of leg columns
     B = 16.0 * n + 68.0 * m
     if rank == 0:
@@ -1016,7 +1083,7 @@ def features_workload(a, lib, rk):
                          "frac": B / (dev_ms * 1e-3) / HBM_PEAK, "traffic": None,
                          "algorithmic_bytes_per_tick": B / n, "duration_ms": dev_ms},
         }
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             sys.path.insert(0, str(ROOT / "oracle"))
             import pyoracle
             ns = min(n, 20_000_000)

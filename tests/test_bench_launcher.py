@@ -47,6 +47,22 @@ def test_gpus_one_is_a_single_process():
     assert line["n_gpus"] == 1 and len(line["rank_ms_per_step"]) == 1
 
 
+def test_stub_dump_outputs_writes_each_ranks_result(tmp_path):
+    """`--dump-outputs DIR` through the command line, two ranks: rank 0 writes
+    acc.npy and rank 1 acc.rank1.npy, both float64 and both the all-reduced sum
+    the line reports (what the last timed step left)."""
+    import numpy as np
+    r = subprocess.run([sys.executable, str(REPO / "bench.py"), "--gpus", "2", "--stub", "--steps", "2",
+                        "--warmup", "0", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, env=_env(), timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = _json_line(r.stdout)
+    assert sorted(f.name for f in (tmp_path / "out").iterdir()) == ["acc.npy", "acc.rank1.npy"]
+    for name in ("acc.npy", "acc.rank1.npy"):
+        v = np.load(tmp_path / "out" / name)
+        assert v.dtype == np.float64 and v.shape == (1,) and v[0] == line["all_reduce_check"]
+
+
 def test_world_size_mismatch_fails_loudly():
     env = _env()
     env.update(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")
@@ -78,6 +94,36 @@ def test_c2_line_finds_its_pmc_traffic(tmp_path, monkeypatch):
     assert t is None and "00112233aabbccdd" in note, note
     t, note = bench.load_traffic(dom, 1_000, 1000, "00112233aabbccdd")
     assert t is None and "shape" in note, note
+
+
+def test_dump_outputs_is_bounded_and_repeatable(tmp_path, monkeypatch):
+    """--dump-outputs: every array as float64 .npy; one above its share of the cap
+    is a sample of its elements in memory order at the same seeded indices in every
+    run, and the whole dump stays under 64 MB."""
+    import types
+    import numpy as np
+    import torch
+    sys.path.insert(0, str(REPO))
+    import bench
+    assert bench.DUMP_CAP <= 64_000_000 - 64 * 1024  # room for the .npy headers
+    monkeypatch.setattr(bench, "DUMP_CAP", 8 * 3 * 1000)  # 1000 elements per array
+    big = torch.arange(5000 * 7, dtype=torch.float64).reshape(7, 5000)
+    arrays = {"small_i32": torch.arange(12, dtype=torch.int32).reshape(3, 4), "big": big,
+              "host": np.linspace(0.0, 1.0, 9)}
+    rk = types.SimpleNamespace(rank=0, world=1)
+    bench.dump_outputs(tmp_path / "a", rk, arrays)
+    bench.dump_outputs(tmp_path / "b", rk, arrays)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert sorted(got) == sorted(arrays)
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert np.array_equal(got["small_i32"], np.arange(12.0).reshape(3, 4))
+    assert np.array_equal(got["host"], arrays["host"])
+    s = got["big"]
+    assert s.shape == (1000,) and (np.diff(s) >= 0).all() and len(np.unique(s)) > 900
+    assert set(s.tolist()) <= set(range(5000 * 7))  # the flat array's own elements (value == index here)
+    for name, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{name}.npy"))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 8 * 3 * 1000 + 3 * 256
 
 
 def test_mfma_fraction_counts_flops_not_instructions(monkeypatch):

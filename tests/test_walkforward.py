@@ -8,15 +8,12 @@ request equals every window evaluated on its own.  GPU: the engine's block
 request against per-window oracle runs (windows built from synthetic ticks by
 the GPU feature extractor).
 """
-import pathlib
-
 import numpy as np
 import pytest
 
 from hhmm_amd import features as F, synth, walkforward as W
 from tolerances import compare_all
 
-DATA = pathlib.Path("/root/reference/tayal2009/data")
 PARS = ["loglik", "alpha_tk", "alpha_tk_oos", "zstar_t", "logp_zstar"]
 
 
@@ -54,20 +51,6 @@ def test_window_tasks_layout(tmp_path):
     assert [f.name[:10] for f in t0["files"]] == [f"2007.05.0{d}" for d in range(1, 7)]
     assert t0["ins"] == "2007-05-01 09:30:00/2007-05-05 16:30:00"
     assert t0["oos"] == "2007-05-06 09:30:00/2007-05-06 16:30:00"
-
-
-@pytest.mark.skipif(not DATA.exists(), reason="reference tick data not present (GPU box)")
-def test_reference_task_list_has_204_windows(oracle):
-    """12 stocks x (22 - 6 + 1) windows (test-strategy.R:45-59); the first
-    task's in/out-of-sample data through the oracle's extractor."""
-    tasks = W.window_tasks(DATA)
-    assert len(tasks) == 204 and len({t["stock"] for t in tasks}) == 12
-    w = W.load_window(tasks[0], extract=oracle.extract_features)
-    assert w["x"].size > 1000 and w["x_oos"].size > 100
-    for k in ("x", "x_oos"):
-        assert w[k].min() >= 1 and w[k].max() <= 9
-    for k in ("sign", "sign_oos"):
-        assert set(np.unique(w[k])) <= {1, 2}
 
 
 def test_window_data_split_and_coding(oracle):

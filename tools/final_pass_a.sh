@@ -12,7 +12,7 @@ OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- \
-    python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/trace.log 2> $OUT/trace.err \
+    python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/trace.log 2> $OUT/trace.err \
     || { echo "traced bench rc=$?"; tail -20 $OUT/trace.err; exit 1; }
 echo "traced bench ok"
 BENCH="$R/bench.py --no-cpu-baseline --no-check --no-path-gather --steps 1 --warmup 1"

@@ -13,9 +13,9 @@ run() {
   timeout -k 10 240 python -u $R/bench.py "$@" > $O/$name.json 2> $O/$name.err || { echo "FAIL $name rc=$?"; exit 1; }
   echo "ok $name"
 }
-run c2 --steps 20 --warmup 5
+run c2 --full --steps 20 --warmup 5
 for w in c1 c3 c4 c5 n1 n2 f1; do
-  run $w --workload $w --steps 5 --warmup 2
+  run $w --workload $w --full --steps 5 --warmup 2
 done
-run c2-host --workload c2-host --steps 3 --warmup 1
+run c2-host --workload c2-host --full --steps 3 --warmup 1
 exit 0

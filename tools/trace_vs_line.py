@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The C2 bench line against the rocprofv3 kernel trace of the SAME process
-(VERDICT r4 item 2): `bench.py --gpus 1 --steps K --warmup W` run as
+(VERDICT r4 item 2): `bench.py --gpus 1 --steps K --warmup W --full` run as
 `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o trace -- python3 bench.py ...`.
 
   python tools/trace_vs_line.py gpurun_out/TAG/bench_traced.json gpurun_out/TAG/trace TAG [OUT.json]
@@ -54,7 +54,7 @@ def main():
         "tag": tag,
         "kernel": kern,
         "library": line.get("library"),
-        "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps %d --warmup %d" % (K, W),
+        "command": "rocprofv3 --kernel-trace --stats -- python3 bench.py --gpus 1 --steps %d --warmup %d --full" % (K, W),
         "dispatches": len(disp),
         "timed_dispatch_ms": timed,
         "trace_mean_ms": mean_ms,
