@@ -306,7 +306,8 @@ struct ArrayDesc {
  * outside [lo, hi].  Time-major, so each thread streams contiguous rows (the
  * n-major loop that names the first offender in the error message strides by
  * N and took ~0.2 s at C2-host's 2e8 symbols); threads over time ranges for
- * large arrays. */
+ * large arrays.  The distance from lo is taken in unsigned arithmetic: R's
+ * NA_integer_ is INT32_MIN, and INT32_MIN - lo overflows a signed int. */
 static bool any_out_of_range(const int32_t *v, int64_t N, int Tm, const int32_t *T, int32_t lo, int32_t hi)
 {
     const uint32_t span = (uint32_t)(hi - lo);
@@ -317,11 +318,11 @@ static bool any_out_of_range(const int32_t *v, int64_t N, int Tm, const int32_t 
             if (!T) {
                 uint32_t acc = 0;
                 for (int64_t n = 0; n < N; ++n)
-                    acc |= (uint32_t)((uint32_t)(r[n] - lo) > span);
+                    acc |= (uint32_t)((uint32_t)r[n] - (uint32_t)lo > span);
                 bad = acc != 0;
             } else {
                 for (int64_t n = 0; n < N; ++n)
-                    bad |= (t < T[n]) & ((uint32_t)(r[n] - lo) > span);
+                    bad |= (t < T[n]) & ((uint32_t)r[n] - (uint32_t)lo > span);
             }
         }
         return bad;
@@ -889,16 +890,35 @@ static ChunkLayout chunk_layout(const hhmm_request *req, const std::vector<Array
     return L;
 }
 
+/* The pairs a chunk's PAIRS-class slices hold (rows of cnt at a pitch of lead)
+ * must be the pairs its sub-request computes: the kernels write L.P pairs of
+ * every output into slots sized from the slices, so a planner mistake here
+ * would be a device overrun. */
+static int64_t chunk_staged_pairs(const hhmm_request *req, const Shard &c)
+{
+    return c.lead[PAIRS] > 0 ? c.cnt[PAIRS] * (npairs(req) / c.lead[PAIRS]) : -1;
+}
+static bool chunk_pairs_agree(const hhmm_request *req, const Shard &c, const ChunkLayout &L)
+{
+    return chunk_staged_pairs(req, c) == L.P;
+}
+
 /* Sub-shards of a device shard: `n` contiguous ranges of its units (series,
  * or draws for a GRID request split by draws), each a Shard of the request. */
 static std::vector<Shard> split_shard(const hhmm_request *r, const Shard &sh, int64_t n)
 {
     const int64_t S = r->draws.n_draws;
+    if (n <= 1)
+        return {sh};
     /* a GRID shard holding every series splits by draws (rows of the chunk's
      * draws at a pitch of S pairs) when it is a draws shard already or has
-     * fewer series than chunks; every other shard splits by series */
+     * fewer series than chunks; every other shard splits by series.  A draws
+     * shard is known by its layout (its pairs lie at a pitch of S, not packed
+     * over the request's P), not by holding fewer than S draws: at S = 1 it
+     * holds them all.  With one series the two layouts coincide and the shard
+     * splits by draws through `cnt[SERIES] < n`. */
     const bool all_series = sh.cnt[SERIES] == r->data.n_series;
-    const bool draws_shard = sh.lead[PAIRS] == S && sh.cnt[DRAWS] < S;
+    const bool draws_shard = sh.lead[PAIRS] != npairs(r);
     const bool by_draws = r->pairing == HHMM_PAIR_GRID && all_series && (draws_shard || sh.cnt[SERIES] < n);
     const int64_t u0 = by_draws ? sh.off[DRAWS] : sh.off[SERIES];
     const int64_t units = by_draws ? sh.cnt[DRAWS] : sh.cnt[SERIES];
@@ -987,6 +1007,11 @@ static hhmm_status run_on_device(const hhmm_request *req, hhmm_result *res, cons
         const ChunkLayout &L = lay.back();
         if (L.P < 1) {
             set_error("internal: shard describes no pairs");
+            return HHMM_ERR_INVALID_ARGUMENT;
+        }
+        if (!chunk_pairs_agree(req, c, L)) {
+            set_error("internal: a chunk stages %lld pairs for a sub-request of %lld",
+                      (long long)chunk_staged_pairs(req, c), (long long)L.P);
             return HHMM_ERR_INVALID_ARGUMENT;
         }
         slot_bytes = std::max(slot_bytes, L.total);
@@ -1452,7 +1477,7 @@ static hhmm_status segment_run(const hhmm_request *req, hhmm_result *res, const 
         return HHMM_ERR_INVALID_ARGUMENT;
     }
     /* both calls check the window's data: the summary marks a bad pair's record
-     * (NaN log scale) so that every rank chaining it flags the pair */
+     * (a log scale of +infinity) so that every rank chaining it flags the pair */
     return launch_all(&r2, rr, npairs(&r2), ws, (hipStream_t)stream, seg, phase, true);
 }
 
@@ -1525,6 +1550,11 @@ hhmm_status hhmm_selftest_pipeline(const hhmm_request *req, hhmm_result *res, in
     for (const Shard &sh : make_shards(req, nshards)) {
         for (const Shard &c : split_shard(req, sh, nchunks)) {
             const ChunkLayout L = chunk_layout(req, arrays, c, ragged);
+            if (L.P < 1 || !chunk_pairs_agree(req, c, L)) { /* run_on_device's guard */
+                set_error("pipeline self-test: a chunk stages %lld pairs for a sub-request of %lld",
+                          (long long)chunk_staged_pairs(req, c), (long long)L.P);
+                return HHMM_ERR_INVALID_ARGUMENT;
+            }
             std::vector<char> slot(L.total, 0);
             /* the gather, as run_on_device stages it, checked byte for byte
              * against a row-by-row pack of the same slice */

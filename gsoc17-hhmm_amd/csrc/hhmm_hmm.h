@@ -234,7 +234,44 @@ __device__ __forceinline__ void load_params(PairParams<MODEL, K> &pp, const DevA
  * kRowBatch at a time, all loads of a batch in flight together (a load per
  * row followed by its LDS store costs one HBM round trip per row). */
 constexpr int kRowBatch = 4;
-template <int K, bool LOG>
+
+/* The lane-per-pair Viterbi (vit_step) reads log A and the log emissions with
+ * every NaN entry replaced by -inf, once per pair at load time.  The
+ * reference's `if (logp > delta)` from -inf ignores a NaN candidate and a
+ * -inf one alike (neither moves delta or the back-pointer), so the swap
+ * changes no delta and no back-pointer; and with no NaN parameter left, no
+ * candidate after the Q3 step is NaN (finite or -inf terms only: an infinite
+ * parameter is outside the contract), which is what lets vit_step start its
+ * running max from candidate 0 instead of from -inf.  Without the swap a NaN
+ * candidate 0 (A_ij[0, j] = NaN) became that start: the first finite
+ * candidate then took the value but not the back-pointer. */
+__device__ __forceinline__ double vit_nonan(double v) { return isnan(v) ? dev_ninf() : v; }
+
+/* load_params<LOG> for vit_step: log A without NaN; a Gaussian state with a NaN
+ * mu or sigma gets the constants that make gauss_lpdf -inf at every finite x
+ * (c0 = -inf, z = (x - 0) * 0). */
+template <int MODEL, int K>
+__device__ __forceinline__ void load_vit_params(PairParams<MODEL, K> &pp, const DevArgs &a, int64_t d)
+{
+    load_params<MODEL, K, true>(pp, a, d);
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            pp.A[i][j] = vit_nonan(pp.A[i][j]);
+    if constexpr (ModelTraits<MODEL>::kGauss) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const bool nan = isnan(pp.mu[k]) || isnan(pp.c0[k]) || isnan(pp.isig[k]);
+            pp.mu[k] = nan ? 0.0 : pp.mu[k];
+            pp.isig[k] = nan ? 0.0 : pp.isig[k];
+            pp.c0[k] = nan ? dev_ninf() : pp.c0[k];
+        }
+    }
+}
+
+/* VIT: the table feeds vit_step (LOG only): NaN -> -inf, see vit_nonan. */
+template <int K, bool LOG, bool VIT = false>
 __device__ __forceinline__ bool fill_table(double2 *slab, const DevArgs &a, int64_t d)
 {
     constexpr int KP = (K + 1) / 2;
@@ -258,6 +295,10 @@ __device__ __forceinline__ bool fill_table(double2 *slab, const DevArgs &a, int6
                     if (LOG) {
                         v0 = dev_cr_log(v0);
                         v1 = dev_cr_log(v1);
+                    }
+                    if (VIT) {
+                        v0 = vit_nonan(v0);
+                        v1 = vit_nonan(v1);
                     }
                     slab[((l0 + r) * KP + kp) * 64] = make_double2(v0, v1);
                 }
@@ -743,15 +784,16 @@ __device__ __forceinline__ void emit_posteriors(const DevArgs &a, int64_t p, int
 
 
 /* The device entry's data check done inline by a whole-series sweep that reads
- * x anyway (HHMM_PAIR_INVALID_DATA): the running max of x - 1 as unsigned (an
- * x < 1 wraps above L), one sub and one max per symbol; steps at or past the
+ * x anyway (HHMM_PAIR_INVALID_DATA): the running max of x - 1, subtracted in
+ * unsigned arithmetic (an x < 1 wraps above L; INT32_MIN, R's NA_integer_,
+ * would overflow a signed x - 1), one sub and one max per symbol; steps at or past the
  * lane's own length count only on the wave's partial chunks (FULL: none). */
 template <int C, bool FULL>
 __device__ __forceinline__ void xcheck_acc(uint32_t &xm, const Obs (&o)[C], int c, int Tp)
 {
 #pragma unroll
     for (int v = 0; v < C; ++v)
-        xm = max(xm, (FULL || c * C + v < Tp) ? (uint32_t)(o[v].x - 1) : 0u);
+        xm = max(xm, (FULL || c * C + v < Tp) ? ((uint32_t)o[v].x - 1u) : 0u);
 }
 
 /* Per-lane state of the forward-backward kernel. */
@@ -808,7 +850,7 @@ __device__ __forceinline__ void fwd_chunk(const DevArgs &a, const FbLane<MODEL, 
                 uint32_t w = 0;
 #pragma unroll
                 for (int v = 0; v < C; ++v)
-                    w |= ((uint32_t)(cur[v].x - 1) & 15u) << (4 * v);
+                    w |= (((uint32_t)cur[v].x - 1u) & 15u) << (4 * v);
                 at(a.xpk + ln.Qs * (int64_t)(c - ln.cb), (uint32_t)ln.q * 4u) = w;
             }
         }
@@ -1322,9 +1364,13 @@ __device__ __forceinline__ void vit_step(double (&dl)[K], const PairParams<MODEL
                                          const Obs &o, uint32_t &word, int slot)
 {
     /* NANIN: delta_{t-1} may hold NaN -- only the step after the t = 1 row of
-     * Q3.  Every later delta is a max over candidates that include a non-NaN
-     * one (state K's row at t = 2, then every state), so the running max can
-     * start from the first candidate instead of from fmax(-inf, candidate). */
+     * Q3.  Every later delta is a max over non-NaN candidates (delta_{t-1}
+     * comes out of an fmax from -inf, and the callers' log A and log
+     * emissions hold no NaN: load_vit_params, fill_table<.., VIT>), so the
+     * running max can start from the first candidate instead of from
+     * fmax(-inf, candidate).  It must not with a NaN candidate 0: the next
+     * candidate would take the value through fmax but, failing `>` against
+     * NaN, not the back-pointer. */
     constexpr int BITS = bp_bits(K);
     constexpr int STEPB = K * BITS;
     double nd[K];
@@ -1412,9 +1458,9 @@ __device__ __forceinline__ void viterbi_block(const DevArgs &a, uint32_t block)
     double2 *slab = lds + (size_t)wave * a.L * KP * 64 + lane;
 
     PairParams<MODEL, K> pp;
-    load_params<MODEL, K, true>(pp, a, d);
+    load_vit_params<MODEL, K>(pp, a, d);
     if constexpr (ModelTraits<MODEL>::kDiscrete)
-        fill_table<K, true>(slab, a, d);
+        fill_table<K, true, true>(slab, a, d);
     const SeriesPtrs sp = series_ptrs<MODEL, VAUX>(a, n);
     static_assert(!PK || (!VAUX && !ModelTraits<MODEL>::kGauss && CV == 8), "packed symbols: 8-step chunks, x only");
     const int pkrows = (a.Tmax + CV - 1) / CV;
@@ -1639,9 +1685,9 @@ __device__ __forceinline__ void fbv_block(const DevArgs &a, uint32_t block)
     ln.slab = slab;
     PairParams<MODEL, K> lpp; /* log A for the max-plus half */
     load_params<MODEL, K, false>(ln.pp, a, d);
-    load_params<MODEL, K, true>(lpp, a, d);
+    load_vit_params<MODEL, K>(lpp, a, d);
     fill_table<K, false>(slab, a, d);
-    fill_table<K, true>(slab + tab, a, d);
+    fill_table<K, true, true>(slab + tab, a, d);
     if constexpr (!(MODE & FB_RN1)) {
         if (wave_any(!renorm_sparse_safe<MODEL, K>(ln.pp, slab, a.L))) {
             fbv_block<MODEL, K, MODE | FB_RN1>(a, block); /* per-step renormalisation (renorm_sparse_safe) */
@@ -1768,7 +1814,7 @@ __device__ __forceinline__ uint32_t pack_chunk(const Obs (&cur)[8])
     uint32_t w = 0;
 #pragma unroll
     for (int v = 0; v < 8; ++v)
-        w |= ((uint32_t)(cur[v].x - 1) & 15u) << (4 * v);
+        w |= (((uint32_t)cur[v].x - 1u) & 15u) << (4 * v);
     return w;
 }
 
@@ -1952,8 +1998,8 @@ __device__ __forceinline__ void vfb_block(const DevArgs &a, int64_t gwave)
     {
         /* ---- phase 1: Viterbi over x ---- */
         PairParams<MODEL, K> lpp;
-        load_params<MODEL, K, true>(lpp, a, d);
-        fill_table<K, true>(slab, a, d);
+        load_vit_params<MODEL, K>(lpp, a, d);
+        fill_table<K, true, true>(slab, a, d);
         int64_t n, dd;
         pair_coords(a, p, n, dd);
         const SeriesPtrs sp = series_ptrs<MODEL, false>(a, n);

@@ -436,7 +436,7 @@ __global__ void __launch_bounds__(256) data_check_kernel(const int32_t *v, int v
                      (!w || ((uintptr_t)w % 16) == 0);
     bool bad[kDcSeries] = {};
     auto test = [&](int hi, int t, int j, int val) {
-        bad[j] |= (t < Tn[j]) & ((uint32_t)(val - 1) >= (uint32_t)hi);
+        bad[j] |= (t < Tn[j]) & ((uint32_t)val - 1u >= (uint32_t)hi);
     };
     for (int64_t s0 = (int64_t)blockIdx.y * kDcSteps; s0 < Tmax; s0 += (int64_t)gridDim.y * kDcSteps) {
     const int t0 = (int)s0;
@@ -487,9 +487,14 @@ __global__ void __launch_bounds__(256) data_check_kernel(const int32_t *v, int v
 /* pair_status[p] = HHMM_PAIR_INVALID_DATA for the pairs of flagged series and
  * of series whose T[n] / T_oos[n] lies outside 1..T_max / 1..T_oos_max.
  * Segment windows: the summary call has no pair_status, so a bad
- * pair's summary carries a NaN log scale (field 2K^2 + 1) instead; every rank
- * that chains it (hhmm_amd.segment.boundaries) then receives a NaN in the
- * entering state or the leaving beta, and the finish call flags the pair. */
+ * pair's summary carries a log scale (field 2K^2 + 1) of +infinity instead.
+ * The chain (hhmm_amd.segment.boundaries) forwards that marker by value into
+ * the log-scale field (field K) of the state entering and of the beta leaving
+ * every window of the pair, and the finish call flags the pair on that field
+ * alone.  No draw produces the marker: a log scale is a sum of logs of
+ * densities and of likelihood ratios, +infinity only for an infinite
+ * parameter, and a NaN draw (which does reach every boundary field as NaN)
+ * leaves the pair what one call over the whole series reports, PAIR_OK. */
 __global__ void __launch_bounds__(256) data_mark_kernel(const DevArgs a, const int32_t *T_oos, int Toos_max)
 {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -504,16 +509,14 @@ __global__ void __launch_bounds__(256) data_mark_kernel(const DevArgs a, const i
         bad |= T_oos[n] < 1 || T_oos[n] > Toos_max;
     if (a.seg_phase == 1) {
         if (bad && a.seg_sum)
-            a.seg_sum[p + a.P * (int64_t)(2 * a.K * a.K + 1)] = __builtin_nan("");
+            a.seg_sum[p + a.P * (int64_t)(2 * a.K * a.K + 1)] = __builtin_inf();
         return;
     }
     if (a.seg_phase == 2) {
-        for (int f = 0; f <= a.K; ++f) {
-            if (a.seg_nofirst && a.seg_enter)
-                bad |= isnan(a.seg_enter[p + a.P * (int64_t)f]);
-            if (a.seg_nolast && a.seg_leave)
-                bad |= isnan(a.seg_leave[p + a.P * (int64_t)f]);
-        }
+        if (a.seg_nofirst && a.seg_enter)
+            bad |= a.seg_enter[p + a.P * (int64_t)a.K] == __builtin_inf();
+        if (a.seg_nolast && a.seg_leave)
+            bad |= a.seg_leave[p + a.P * (int64_t)a.K] == __builtin_inf();
     }
     if (bad)
         a.pair_status[p] = HHMM_PAIR_INVALID_DATA;

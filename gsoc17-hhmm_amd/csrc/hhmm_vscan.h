@@ -283,9 +283,9 @@ __global__ void __launch_bounds__(kBlock) vs_prod_tie_kernel(const DevArgs a)
     double2 *slab = lds + (size_t)wave * a.L * KP * 64 + lane;
     if (work) {
         PairParams<MODEL, K> pp;
-        load_params<MODEL, K, true>(pp, a, v.d);
+        load_vit_params<MODEL, K>(pp, a, v.d);
         if constexpr (ModelTraits<MODEL>::kDiscrete)
-            fill_table<K, true>(slab, a, v.d);
+            fill_table<K, true, true>(slab, a, v.d);
         const SeriesPtrs sp = series_ptrs<MODEL, VAUX>(a, v.n);
         vs_tie_row<MODEL, K>(a, v, pp, slab, sp, ldexp(1.0, 52 - kc), ldexp(1.0, kc - 52), (double)par, row,
                              par ? a.vs_m1 : a.vs_m);
@@ -328,9 +328,9 @@ __global__ void __launch_bounds__(kBlock) vs_prod_kernel(const DevArgs a)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double2 *slab = lds + (size_t)wave * a.L * KP * 64 + lane;
     PairParams<MODEL, K> pp;
-    load_params<MODEL, K, true>(pp, a, v.d);
+    load_vit_params<MODEL, K>(pp, a, v.d);
     if constexpr (ModelTraits<MODEL>::kDiscrete)
-        fill_table<K, true>(slab, a, v.d);
+        fill_table<K, true, true>(slab, a, v.d);
     bool tie = false;
     const SeriesPtrs sp = series_ptrs<MODEL, VAUX>(a, v.n);
     if constexpr (GRID && ModelTraits<MODEL>::kDiscrete) {
@@ -674,7 +674,7 @@ __device__ __forceinline__ void vs_sp_setup(const DevArgs &a, int64_t d, double 
     ln.j = lane & 3;
     ln.js = min(ln.j, K - 1);
     PairParams<MODEL, K> pp;
-    load_params<MODEL, K, true>(pp, a, d);
+    load_vit_params<MODEL, K>(pp, a, d);
 #pragma unroll
     for (int i = 0; i < K; ++i) {
         double v = pp.A[i][0];
@@ -700,7 +700,7 @@ __device__ __forceinline__ void vs_sp_setup(const DevArgs &a, int64_t d, double 
     if constexpr (ModelTraits<MODEL>::kDiscrete) {
         double *col = ldsd + lane;
         for (int l = 0; l < a.L; ++l)
-            col[l * 64] = dev_cr_log(draw2<K>(a.phi_k, a, d, ln.js, l, K));
+            col[l * 64] = vit_nonan(dev_cr_log(draw2<K>(a.phi_k, a, d, ln.js, l, K)));
     }
     if constexpr (ModelTraits<MODEL>::kTayal) {
         double *rows = ldsd + (size_t)a.L * 64 + lane;
@@ -1228,9 +1228,9 @@ __global__ void __launch_bounds__(kBlock) vs_replay_kernel(const DevArgs a)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double2 *slab = lds + (size_t)wave * a.L * KP * 64 + lane;
     PairParams<MODEL, K> pp;
-    load_params<MODEL, K, true>(pp, a, v.d);
+    load_vit_params<MODEL, K>(pp, a, v.d);
     if constexpr (ModelTraits<MODEL>::kDiscrete)
-        fill_table<K, true>(slab, a, v.d);
+        fill_table<K, true, true>(slab, a, v.d);
     const SeriesPtrs sp = series_ptrs<MODEL, VAUX>(a, v.n);
     double dl[K];
     uint32_t word = 0;

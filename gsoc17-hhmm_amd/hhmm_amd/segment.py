@@ -168,9 +168,17 @@ class SegmentWindow:
             out[name] = np.ndarray(arr.shape, dtype=arr.dtype, buffer=flat.copy(),
                                    order="F" if arr.flags.f_contiguous else "C")
         # per pair: HHMM_PAIR_INVALID_DATA where this window's data, or a chained
-        # summary of another window (a NaN log scale), breaks a data-block bound
+        # summary of another window (BAD_DATA in its log scale), breaks a data-block bound
         out["pair_status"] = self.status.cpu().numpy()
         return out
+
+
+# The log scale (field 2K^2 + 1) of a summary whose window breaks a data-block
+# bound, and the log scale (field K) of the boundaries of such a pair: the one
+# value the finish call flags HHMM_PAIR_INVALID_DATA on.  No draw produces it
+# (a NaN draw makes every field NaN and stays PAIR_OK, as in one call over the
+# whole series), so it is forwarded by value, never through the arithmetic.
+BAD_DATA = np.inf
 
 
 def _renorm(v, sc):
@@ -184,11 +192,17 @@ def boundaries(summaries, K):
     """Chains the windows' summaries ([2K^2 + 3, P] each, window order) into
     the state entering every window, beta leaving every window ([K + 1, P]:
     the vector up to scale, then its log scale; None where the window is the
-    first / the last) and the log-likelihood of the whole series per pair."""
+    first / the last) and the log-likelihood of the whole series per pair.
+    A pair with BAD_DATA in some window's summary gets BAD_DATA as the log scale
+    of every boundary (every window's finish call then flags it) and a NaN
+    log-likelihood."""
     R = len(summaries)
     sums = [np.asarray(s, dtype=np.float64) for s in summaries]
     P = sums[0].shape[1]
     KK = K * K
+    bad = np.zeros(P, dtype=bool)
+    for s in sums:
+        bad |= s[2 * KK + 1] == BAD_DATA
 
     def SF(r):  # [P, K, K]
         return sums[r][:KK].T.reshape(P, K, K)
@@ -214,4 +228,8 @@ def boundaries(summaries, K):
         bsc = bsc + sums[r][2 * KK + 1] + LN2 * sums[r][2 * KK + 2]
         b, bsc = _renorm(b, bsc)
         leave[r - 1] = np.vstack([b, bsc[None]])
+    for v in enter + leave:
+        if v is not None:
+            v[K, bad] = BAD_DATA
+    loglik[bad] = np.nan
     return enter, leave, loglik

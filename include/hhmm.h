@@ -349,6 +349,10 @@ hhmm_status hhmm_run_device(const hhmm_request *req, hhmm_result *res,
  *       likewise; unused for the last window), the scan's phases 2 and 3:
  *       loglik (last window only), alpha_tk, beta_tk, ungamma_tk, gamma_tk of
  *       the window's steps.
+ * Both calls check the window's data block.  A pair whose window breaks a
+ * bound leaves the summary call with a log scale of +infinity; the chain puts
+ * +infinity into the log scale (field K) of `enter` and `leave` of every window
+ * of that pair, and the finish call reports HHMM_PAIR_INVALID_DATA for it.
  * The caller all-gathers the ranks' summaries (K x K per pair: 2K^2 + 3
  * doubles) and chains them (hhmm_amd.segment.boundaries; dist.gqs_tsplit).
  * HMM family at K <= 8 (hmm, hmm-multinom, semisup, tayal) and hmm /

@@ -114,6 +114,110 @@ def test_validate_rejects_out_of_range_data(engine):
     assert _validate(engine, pr, host=0) == _abi.OK
 
 
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1   # INT32_MIN is R's NA_integer_
+
+# (model, data-block array, its declared upper bound, the lengths that bound its valid steps)
+RANGE_ARRAYS = [
+    ("hmm-multinom", "x", "L", "T"),
+    ("hmm-multinom-semisup", "g", "G", "T"),
+    ("hhmm-tayal2009", "sign", 2, "T"),
+    ("hhmm-tayal2009-lite", "x_oos", "L", "T_oos"),
+    ("hhmm-tayal2009-lite", "sign_oos", 2, "T_oos"),
+]
+RANGE_IDS = [f"{m}-{k}" for m, k, _, _ in RANGE_ARRAYS]
+OFFENDERS = ["0", "-1", "hi+1", "INT32_MAX", "INT32_MIN"]
+
+
+def _range_request(model, key, hi, at=None, offender=None, lengths=None):
+    """A clean N=3 request; `at` = (n, t) takes the offending value, `lengths` = (name, values) makes it ragged."""
+    data, draws = synth.GENERATORS[model](N=3, S=2, T=12, T_oos=12) if model.endswith("-lite") else \
+        synth.GENERATORS[model](N=3, S=2, T=12)
+    hi = int(data[hi]) if isinstance(hi, str) else hi
+    if at is not None:
+        a = np.array(data[key], dtype=np.int64)
+        a[at] = {"0": 0, "-1": -1, "hi+1": hi + 1, "INT32_MAX": INT32_MAX, "INT32_MIN": INT32_MIN}[offender]
+        data[key] = a
+    if lengths is not None:
+        data[lengths[0]] = np.array(lengths[1], dtype=np.int32)
+    return api.PreparedRequest(model, data, draws, ["loglik"])
+
+
+@pytest.mark.parametrize("offender", OFFENDERS)
+@pytest.mark.parametrize("model,key,hi,_len", RANGE_ARRAYS, ids=RANGE_IDS)
+def test_validate_range_check_every_array(engine, model, key, hi, _len, offender):
+    """Every bounded int array of the data block (x 1..L, g 1..G, sign 1..2 and the
+    out-of-sample pair), with offenders on both sides of the range and at both ends of
+    int32: INT32_MIN is R's NA_integer_, the value the check exists to reject, and
+    `value - lower` must not be formed in signed arithmetic for it."""
+    for at in [(0, 0), (1, 5), (2, 11)]:
+        pr = _range_request(model, key, hi, at, offender)
+        assert _validate(engine, pr) == _abi.ERR_INVALID_ARGUMENT, (at, offender)
+        msg = engine.hhmm_last_error().decode()
+        assert msg.startswith(f"{key}[{at[0]}, {at[1] + 1}] = "), msg   # the offender is named, 1-based in t
+    assert _validate(engine, _range_request(model, key, hi)) == _abi.OK, engine.hhmm_last_error()
+
+
+@pytest.mark.parametrize("offender", OFFENDERS)
+@pytest.mark.parametrize("model,key,hi,length", RANGE_ARRAYS, ids=RANGE_IDS)
+def test_validate_range_check_ragged(engine, model, key, hi, length, offender):
+    """Ragged lengths (T / T_oos given): a series' last valid step is checked, the
+    step after it is padding and may hold anything."""
+    Tn = [12, 7, 1]
+    assert _validate(engine, _range_request(model, key, hi, lengths=(length, Tn))) == _abi.OK, \
+        engine.hhmm_last_error()
+    for n in range(3):
+        pr = _range_request(model, key, hi, (n, Tn[n] - 1), offender, lengths=(length, Tn))
+        assert _validate(engine, pr) == _abi.ERR_INVALID_ARGUMENT, (n, offender)
+        assert engine.hhmm_last_error().decode().startswith(f"{key}[{n}, {Tn[n]}] = ")
+        if Tn[n] < 12:
+            pr = _range_request(model, key, hi, (n, Tn[n]), offender, lengths=(length, Tn))
+            assert _validate(engine, pr) == _abi.OK, (n, offender, engine.hhmm_last_error())
+
+
+@pytest.fixture(scope="module")
+def large_request():
+    """N * T_max = 2^22 symbols, where the range scan splits T over host threads;
+    only x (16 MB) is large: one draw, loglik alone."""
+    N, T = 64, 1 << 16
+    _, draws = synth.hmm_multinom(N=1, S=1, T=2, K=4, L=9)
+    x = np.asfortranarray(np.random.default_rng(3).integers(1, 10, size=(N, T)), dtype=np.int32)
+    lengths = np.full(N, T, dtype=np.int32)
+    lengths[5] = T - 4
+    lengths[N - 1] = T // 2 + 1
+    pr = api.PreparedRequest("hmm-multinom", {"K": 4, "L": 9, "x": x, "T": lengths}, draws, ["loglik"])
+    assert pr.keep[0].shape == (N, T) and pr.keep[0].flags.f_contiguous
+    return pr, pr.keep[0], pr.req.data.T, lengths
+
+
+@pytest.mark.parametrize("ragged", [False, True], ids=["full", "ragged"])
+@pytest.mark.parametrize("offender", [0, 10, INT32_MAX, INT32_MIN])
+def test_validate_range_check_threaded(engine, large_request, ragged, offender):
+    """The threaded scan: a single offender in the first row, a middle row and the
+    last row and column is found whichever thread's range holds it; in the padding
+    past a ragged length it is not one."""
+    pr, x, T_ptr, lengths = large_request
+    N, T = x.shape
+    pr.req.data.T = T_ptr if ragged else None
+    assert _validate(engine, pr) == _abi.OK, engine.hhmm_last_error()
+    spots = [(0, 0), (N // 2, T // 2), (N - 2, T - 1)]
+    spots.append((N - 1, T // 2) if ragged else (N - 1, T - 1))   # the ragged last series ends at T/2 + 1
+    for n, t in spots:
+        keep = x[n, t]
+        x[n, t] = offender
+        st, msg = _validate(engine, pr), engine.hhmm_last_error().decode()
+        x[n, t] = keep
+        assert st == _abi.ERR_INVALID_ARGUMENT, (n, t)
+        assert msg.startswith(f"x[{n}, {t + 1}] = {offender} "), msg
+    if ragged:
+        for n, t in [(5, T - 4), (5, T - 1), (N - 1, T // 2 + 1), (N - 1, T - 1)]:
+            keep = x[n, t]
+            x[n, t] = offender
+            st = _validate(engine, pr)
+            x[n, t] = keep
+            assert st == _abi.OK, (n, t, engine.hhmm_last_error())
+    assert _validate(engine, pr) == _abi.OK
+
+
 def test_validate_rejects_bad_requests(engine):
     pr = _prepared()
     pr.req.abi_version = 99

@@ -152,6 +152,36 @@ def test_multinom_schedules_ragged(engine, oracle, outs, flags):
     _run(engine, oracle, "hmm-multinom", data, bad, draws, outs, [5, 17, 41, 60, 299], pairing="zip", flags=flags)
 
 
+INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
+# The phased sweep (vfb_kernel) is a lane-per-pair schedule: at K <= 4 a batch below 131072 pairs decodes
+# state-parallel instead (use_vit_states) and the request falls back to fb_kernel + viterbi_sp_kernel, so
+# FLAG_VIT_LANES (_LANES) is what puts this small batch on it; the default dispatch runs beside it.
+EXTREME_SCHEDULES = [s for s in SCHEDULES if s[0] in ("fb", "log-space")] + [
+    ("phased-sweep", C2_PARS, _LANES),                              # vfb_kernel: inline, while it packs x
+    ("default-dispatch", C2_PARS, 0),                               # fb_kernel inline + viterbi_sp_kernel
+]
+
+
+@pytest.mark.parametrize("outs,flags", [s[1:] for s in EXTREME_SCHEDULES], ids=[s[0] for s in EXTREME_SCHEDULES])
+def test_multinom_extreme_symbols(engine, oracle, outs, flags):
+    """The ends of int32 on the three checks that differ (inline in fb_sweep, the
+    separate check pass, inline in the phased sweep, whose 4-bit packed symbols
+    then feed its other phases) and on the default dispatch of this batch:
+    INT32_MIN is R's NA_integer_, where `x - 1` wraps (formed in unsigned
+    arithmetic), and INT32_MAX the largest index a table lookup could form.
+    The kernels clamp the symbol before they index with it, so the series is
+    flagged and nothing else changes; the same value in padding is no violation."""
+    N, T = 130, 70
+    data, draws = synth.hmm_multinom(N=N, S=N, T=T, K=4, L=9, seed=12)
+    Tn = np.random.default_rng(6).integers(40, T + 1, size=N).astype(np.int32)
+    Tn[3], Tn[70], Tn[129] = T, 55, 41
+    data = dict(data, T=Tn)
+    bad = _corrupt(data, "x", 3, 0, INT32_MIN)            # step 0 (the init row)
+    bad = _corrupt(bad, "x", 70, 54, INT32_MAX)           # the series' last valid step
+    bad = _corrupt(bad, "x", 129, 41, INT32_MIN)          # t = T[129]: padding, in the final (two-lane) wave
+    _run(engine, oracle, "hmm-multinom", data, bad, draws, outs, [3, 70], pairing="zip", flags=flags)
+
+
 def test_multinom_check_past_grid_y_limit(engine, oracle):
     """T_max above 65535 strips of 64 steps (4,194,240) -- the check
     kernel caps grid.y and loops over strips, so the launch still succeeds and a bad

@@ -152,11 +152,52 @@ def test_two_ranks_gqs_tsplit(engine, oracle, tmp_path, model, kw):
     compare("gamma_tk", gamma, ref["gamma_tk"])
 
 
+@pytest.mark.parametrize("K", [4, 12])
+def test_segment_nan_draw_is_not_bad_data(engine, oracle, K):
+    """A NaN draw parameter (phi_k[1, 0, :]) is not a data-block violation: split
+    over three windows, every finish call reports the pair_status hhmm_run_device
+    gives the whole series, which is the oracle's -- PAIR_OK, with a NaN loglik --
+    and the pairs of the other draws are bit-equal to the clean run.  (The NaN
+    reaches every boundary field of the spoiled draw's pairs, so the bad-data
+    marker of a segment summary must be one that parameters cannot produce.)"""
+    from hhmm_amd import _abi, segment
+    from test_gpu_host_pipeline import _dev
+    model, S, R = "hmm-multinom", 3, 3
+    data, draws = synth.hmm_multinom(N=2, S=S, T=600, K=K, L=9)
+    nan = {k: np.array(v, copy=True) for k, v in draws.items()}
+    nan["phi_k"][1, 0, :] = np.nan
+    wins = segment.windows(600, R)
+    pars = ["loglik", "gamma_tk"]
+
+    def run(d):
+        runs = [segment.SegmentWindow(engine, model, segment.slice_time(data, a, b), d, pars, i == 0, i == R - 1)
+                for i, (a, b) in enumerate(wins)]
+        sums = [w.summary().cpu().numpy() for w in runs]
+        enter, leave, loglik = segment.boundaries(sums, K)
+        return [w.finish(enter[i], leave[i]) for i, w in enumerate(runs)], loglik
+
+    clean, ll_clean = run(draws)
+    got, ll_nan = run(nan)
+    whole = _dev(engine, model, data, nan, pars, "grid")
+    ref = oracle.gqs(model, data, nan, pars=pars, return_status=True)
+    assert np.array_equal(whole["pair_status"], ref["pair_status"])
+    assert np.all(ref["pair_status"] == _abi.PAIR_OK)
+    hit = np.arange(2 * S) % S == 1  # grid pairing: p = s + S n
+    assert np.all(np.isnan(ref["loglik"][hit])) and np.all(np.isfinite(ref["loglik"][~hit]))
+    for i in range(R):
+        assert np.array_equal(got[i]["pair_status"], whole["pair_status"]), (i, got[i]["pair_status"])
+        assert np.array_equal(got[i]["gamma_tk"][~hit], clean[i]["gamma_tk"][~hit])
+    assert np.array_equal(ll_nan[~hit], ll_clean[~hit])
+    # and the windows, stitched, are the oracle's whole series: NaN where it has NaN
+    compare("loglik", ll_nan, ref["loglik"])
+    compare("gamma_tk", np.concatenate([g["gamma_tk"] for g in got], axis=1), ref["gamma_tk"])
+
+
 @pytest.mark.parametrize("bad_window", [0, 1, 2])
 @pytest.mark.parametrize("model,K", [("hmm-multinom", 4), ("hmm-multinom", 12)])
 def test_segment_bad_data_in_one_window(engine, oracle, model, K, bad_window):
     """an out-of-range symbol in ONE window's slice of one
-    series.  Its summary carries a NaN log scale, so every window's finish call
+    series.  Its summary carries segment.BAD_DATA as its log scale, so every window's finish call
     flags that series' pairs HHMM_PAIR_INVALID_DATA (not only the window that
     holds the bad step) and the chained loglik is NaN there; every other pair
     is OK and equal to the clean run."""

@@ -49,6 +49,43 @@ def test_boundaries_match_direct_products():
             np.testing.assert_allclose(v[:K] * np.exp(v[K] - bl), b, rtol=1e-12)
 
 
+def test_boundaries_forward_the_bad_data_marker_and_nothing_else():
+    """A summary whose window broke a data-block bound carries segment.BAD_DATA in
+    its log scale: that pair, whichever window it came from, gets the marker in the
+    log-scale field of every boundary and a NaN loglik.  A pair whose summaries are
+    NaN throughout (a NaN draw) gets no marker: its boundaries are NaN, not bad data.
+    Every other pair is chained as if neither were there."""
+    rng = np.random.default_rng(8)
+    P, K, R = 6, 3, 3
+    f0 = rng.random((P, K))
+    Fs = [np.repeat(f0[:, None, :], K, axis=1)] + [rng.random((P, K, K)) for _ in range(R - 1)]
+    Qs = [rng.random((P, K, K)) for _ in range(R)]
+
+    def sums(mark):
+        g = np.random.default_rng(9)
+        out = [_summary(Fs[r], Qs[r], g.integers(-9, 9, P).astype(float), g.normal(size=P),
+                        g.integers(-9, 9, P).astype(float)) for r in range(R)]
+        if mark:
+            out[0][2 * K * K + 1, 0] = segment.BAD_DATA   # pair 0: the first window
+            out[1][2 * K * K + 1, 2] = segment.BAD_DATA   # pair 2: the middle one
+            out[2][2 * K * K + 1, 5] = segment.BAD_DATA   # pair 5: the last
+            for s in out:
+                s[:, 3] = np.nan                          # pair 3: a NaN draw
+        return out
+
+    enter, leave, loglik = segment.boundaries(sums(True), K)
+    clean_enter, clean_leave, clean_loglik = segment.boundaries(sums(False), K)
+    marked, rest = [0, 2, 5], [1, 4]
+    for v, c in zip(enter + leave, clean_enter + clean_leave):
+        if v is None:
+            assert c is None
+            continue
+        assert np.all(v[K, marked] == segment.BAD_DATA)
+        assert np.all(np.isnan(v[:, 3]))
+        assert np.array_equal(v[:, rest], c[:, rest])
+    assert np.all(np.isnan(loglik[marked + [3]])) and np.array_equal(loglik[rest], clean_loglik[rest])
+
+
 def test_windows_cover_the_series():
     for T in (1, 7, 1000, 1_000_001):
         for R in (1, 2, 3, 8):

@@ -19,10 +19,25 @@ CASES = [
     ("iohmm-hmix", "grid", dict(N=3, S=5)),
     ("hhmm-tayal2009-lite", "grid", dict(N=4, S=3)),
 ]
+# GRID requests of one draw; appended after every older case, so that the older
+# cases keep their positions (their test ids carry them)
+ONE_DRAW_CASES = [
+    # one draw (a posterior mean): with fewer series than shards the shard is
+    # draws-shaped with a single draw, which only its layout tells from a series shard
+    ("hmm-multinom", "grid", dict(N=2, S=1)),
+    ("hmm-multinom", "grid", dict(N=4, S=1)),
+    ("iohmm-hmix", "grid", dict(N=3, S=1)),
+    ("hhmm-tayal2009-lite", "grid", dict(N=5, S=1)),
+    # the all-ones corner, where every shard layout coincides
+    ("hmm-multinom", "grid", dict(N=1, S=1)),
+    ("hmm-multinom", "zip", dict(N=1, S=1)),
+    ("hmm-multinom", "block", dict(N=1, S=1)),
+]
+ALL_CASES = CASES + ONE_DRAW_CASES
 
 
 @pytest.mark.parametrize("nshards", [1, 2, 3, 5, 8])
-@pytest.mark.parametrize("model,pairing,sizes", CASES)
+@pytest.mark.parametrize("model,pairing,sizes", ALL_CASES)
 def test_shards_cover_every_output_element_once(engine, model, pairing, sizes, nshards):
     data, draws = synth.GENERATORS[model](T=23, **sizes)
     data["T"] = np.array([23 - 3 * (i % 4) for i in range(sizes["N"])], dtype=np.int32)
@@ -47,10 +62,11 @@ def test_shard_selftest_rejects_bad_requests(engine):
 PIPE_CASES = CASES + [
     ("hmm-multinom", "grid", dict(N=1, S=11)),     # one series: chunks split the draws
     ("iohmm-reg", "block", dict(N=4, S=12)),
-]
+] + ONE_DRAW_CASES
 
 
-@pytest.mark.parametrize("nshards,nchunks", [(1, 1), (1, 2), (1, 3), (1, 7), (2, 3), (3, 2), (5, 4)])
+@pytest.mark.parametrize("nshards,nchunks", [(1, 1), (1, 2), (1, 3), (1, 7), (2, 3), (3, 2), (5, 4),
+                                             (3, 1), (8, 1), (8, 3), (8, 7)])
 @pytest.mark.parametrize("model,pairing,sizes", PIPE_CASES)
 def test_pipeline_chunks_cover_every_output_element_once(engine, model, pairing, sizes, nshards, nchunks):
     """hhmm_run's host pipeline (VERDICT r5 missing 2): the chunk split of every
