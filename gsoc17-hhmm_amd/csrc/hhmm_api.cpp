@@ -1239,6 +1239,397 @@ static hhmm_status run_sharded(const hhmm_request *req, hhmm_result *res)
     return HHMM_OK;
 }
 
+/* ---------------- hhmm_run_summary: run, reduce over draws, download the summaries ----------------
+ * Ranges of series run one after the other on the device's compute stream:
+ * gather + upload the range's inputs, the request's kernels into a pooled
+ * device slot (the per-draw [P, T, ...] arrays live only there), one summary
+ * launch per reduced output into a pooled summary buffer, then one download of
+ * that buffer, the [P] outputs and pair_status.  What returns is Q/S of what
+ * hhmm_run moves, so the ranges are not overlapped. */
+constexpr uint32_t kSumAllBits = (1u << 19) - 1;
+constexpr uint32_t kSumPairBits = HHMM_OUT_LOGLIK | HHMM_OUT_LOGP_ZSTAR; /* [P]: to `pairs`, not reduced */
+constexpr uint32_t kSumStepBits = kSumAllBits & ~kSumPairBits;
+constexpr uint32_t kSumKAxisBits = HHMM_OUT_UNALPHA | HHMM_OUT_ALPHA | HHMM_OUT_UNBETA | HHMM_OUT_BETA |
+                                   HHMM_OUT_UNGAMMA | HHMM_OUT_GAMMA | HHMM_OUT_OBLIK_TK | HHMM_OUT_ALPHA_OOS |
+                                   HHMM_OUT_UNALPHA_OOS | HHMM_OUT_LOGA | HHMM_OUT_HATPI;
+constexpr size_t kSummaryBudget = (size_t)8 << 30; /* device bytes of one range (and at most 3/4 of what is free) */
+
+/* The hhmm_result field of a per-step output bit. */
+static size_t sum_field(int bit, bool &i32)
+{
+    i32 = false;
+    switch (1u << bit) {
+    case HHMM_OUT_UNALPHA: return offsetof(hhmm_result, unalpha_tk);
+    case HHMM_OUT_ALPHA: return offsetof(hhmm_result, alpha_tk);
+    case HHMM_OUT_UNBETA: return offsetof(hhmm_result, unbeta_tk);
+    case HHMM_OUT_BETA: return offsetof(hhmm_result, beta_tk);
+    case HHMM_OUT_UNGAMMA: return offsetof(hhmm_result, ungamma_tk);
+    case HHMM_OUT_GAMMA: return offsetof(hhmm_result, gamma_tk);
+    case HHMM_OUT_ZSTAR: i32 = true; return offsetof(hhmm_result, zstar_t);
+    case HHMM_OUT_OBLIK_TK: return offsetof(hhmm_result, oblik_tk);
+    case HHMM_OUT_OBLIK_T: return offsetof(hhmm_result, oblik_t);
+    case HHMM_OUT_FFBS: i32 = true; return offsetof(hhmm_result, z_ffbs);
+    case HHMM_OUT_ALPHA_OOS: return offsetof(hhmm_result, alpha_tk_oos);
+    case HHMM_OUT_UNALPHA_OOS: return offsetof(hhmm_result, unalpha_tk_oos);
+    case HHMM_OUT_LOGA: return offsetof(hhmm_result, logA_ij);
+    case HHMM_OUT_HATPI: return offsetof(hhmm_result, hatpi_tk);
+    case HHMM_OUT_HATZ: i32 = true; return offsetof(hhmm_result, hatz_t);
+    case HHMM_OUT_HATL: i32 = true; return offsetof(hhmm_result, hatl_t);
+    case HHMM_OUT_HATX: return offsetof(hhmm_result, hatx_t);
+    default: return (size_t)-1;
+    }
+}
+static bool sum_uses_oos(const hhmm_request *r, int bit)
+{
+    const uint32_t b = 1u << bit;
+    return (b & (HHMM_OUT_ALPHA_OOS | HHMM_OUT_UNALPHA_OOS)) ||
+           (b == HHMM_OUT_ZSTAR && r->model == HHMM_MODEL_TAYAL_LITE);
+}
+static size_t sum_T(const hhmm_request *r, int bit)
+{
+    return (size_t)(sum_uses_oos(r, bit) ? r->data.T_oos_max : r->data.T_max);
+}
+static size_t sum_K(const hhmm_request *r, int bit) { return ((1u << bit) & kSumKAxisBits) ? (size_t)r->data.K : 1; }
+
+/* Where each summary of a range of Nc series sits in the range's summary buffer. */
+struct SumPlan {
+    size_t qoff[32], aoff[32], total;
+};
+static SumPlan sum_plan(const hhmm_request *r, const hhmm_summary_spec *sp, int64_t Nc)
+{
+    SumPlan p{};
+    size_t o = 0;
+    for (int b = 0; b < 32; ++b) {
+        if (!((sp->summarise >> b) & 1u))
+            continue;
+        const size_t cells = (size_t)Nc * sum_T(r, b);
+        p.qoff[b] = o;
+        o += (sizeof(double) * cells * sum_K(r, b) * (size_t)sp->n_probs + 255) & ~(size_t)255;
+        if ((sp->argmax >> b) & 1u) {
+            p.aoff[b] = o;
+            o += (sizeof(int32_t) * cells + 255) & ~(size_t)255;
+        }
+    }
+    p.total = o;
+    return p;
+}
+
+/* `n` contiguous ranges of the series [a0, a1) with all their draws (GRID:
+ * every draw; BLOCK: the series' own blocks) -- never a split by draws. */
+static std::vector<Shard> series_ranges(const hhmm_request *r, int64_t a0, int64_t a1, int64_t n)
+{
+    const int64_t N = r->data.n_series, S = r->draws.n_draws, P = npairs(r);
+    const int64_t B = r->pairing == HHMM_PAIR_BLOCK ? S / N : 0;
+    n = std::max<int64_t>(1, std::min(n, a1 - a0));
+    std::vector<Shard> v;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t a = a0 + (a1 - a0) * i / n, b = a0 + (a1 - a0) * (i + 1) / n;
+        if (r->pairing == HHMM_PAIR_BLOCK)
+            v.push_back(Shard{{a, B * a, B * a}, {b - a, B * (b - a), B * (b - a)}, {N, S, P}});
+        else
+            v.push_back(Shard{{a, 0, S * a}, {b - a, S, S * (b - a)}, {N, S, P}});
+    }
+    return v;
+}
+
+/* Series [a0, a1) of the request on the current device.  `full`: the result
+ * describe() sees (the caller's [P] pointers; placeholders, never
+ * dereferenced, for the per-step outputs, which exist on the device only). */
+static hhmm_status run_summary_on_device(const hhmm_request *req, const hhmm_summary_spec *spec,
+                                         const hhmm_result *full, hhmm_summary_result *out, int64_t a0, int64_t a1,
+                                         bool split_outside, int32_t *status, int64_t *failures)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess)
+        return hip_fail(e, "hipGetDevice");
+    hhmm_request dreq = *req;
+    hhmm_result dres = *full;
+    dres.pair_status = nullptr;
+    std::vector<ArrayDesc> arrays;
+    describe(req, full, &dreq, &dres, arrays);
+    const hhmm_data &d = req->data;
+    const int64_t Pw = npairs(req), N = d.n_series;
+    const bool seq = scan_plan(req->model, d.K, d.T_max, Pw, req->outputs, (uint32_t)req->flags).cl == 0 &&
+                     vscan_chunks(req->model, d.K, req->model == HHMM_MODEL_TAYAL_LITE ? d.T_oos_max : d.T_max, Pw,
+                                  req->outputs, (uint32_t)req->flags) == 0;
+    const int64_t forced = (int64_t)(((uint32_t)req->flags >> 20) & 0xffu);
+    size_t freeb = 0, totalb = 0;
+    if ((e = hipMemGetInfo(&freeb, &totalb)) != hipSuccess)
+        return hip_fail(e, "hipMemGetInfo");
+    const size_t budget = std::min(kSummaryBudget, freeb / 4 * 3);
+    auto ws_of = [&](const Shard &c, int64_t P) {
+        return workspace_bytes(dreq.model, d.K, d.L, d.T_max, d.T_oos_max, P, dreq.outputs, (uint32_t)dreq.flags,
+                               c.cnt[SERIES], dreq.pairing);
+    };
+    auto worst = [&](const std::vector<Shard> &v) {
+        size_t w = 0;
+        for (const Shard &c : v) {
+            const ChunkLayout L = chunk_layout(req, arrays, c, false);
+            w = std::max(w, L.total + ws_of(c, L.P) + sum_plan(req, spec, c.cnt[SERIES]).total);
+        }
+        return w;
+    };
+    int64_t nr = (seq && forced > 0) ? std::min(forced, a1 - a0) : 1;
+    std::vector<Shard> ranges = series_ranges(req, a0, a1, nr);
+    if (forced == 0 || !seq) {
+        for (;;) {
+            const size_t w = worst(ranges);
+            if (w <= budget)
+                break;
+            if (!seq) {
+                set_error("the request runs a parallel scan over T and stays one range, which needs %zu device bytes "
+                          "(budget %zu)", w, budget);
+                return HHMM_ERR_OUT_OF_MEMORY;
+            }
+            if (nr >= a1 - a0) {
+                set_error("a single series needs %zu device bytes of per-draw outputs and workspace, over the "
+                          "budget of %zu: nothing smaller to split into", w, budget);
+                return HHMM_ERR_OUT_OF_MEMORY;
+            }
+            nr = std::min(a1 - a0, std::max(nr + 1, nr + nr / 4));
+            ranges = series_ranges(req, a0, a1, nr);
+        }
+    }
+    if (seq && (ranges.size() > 1 || split_outside))
+        dreq.flags |= (int32_t)(HHMM_FLAG_SCAN_OFF | HHMM_FLAG_VIT_SCAN_OFF);
+
+    /* the [P] outputs among `arrays`, and their place behind the summaries in the download slot */
+    std::vector<size_t> pair_arrays;
+    for (size_t i = 0; i < arrays.size(); ++i)
+        if (arrays[i].output && (arrays[i].dev_slot == (void **)&dres.loglik ||
+                                 arrays[i].dev_slot == (void **)&dres.logp_zstar))
+            pair_arrays.push_back(i);
+    std::vector<ChunkLayout> lay;
+    std::vector<SumPlan> plans;
+    size_t slot_bytes = 0, in_bytes = 0, sum_bytes = 0, host_bytes = 0, wsb = 0;
+    for (const Shard &c : ranges) {
+        lay.push_back(chunk_layout(req, arrays, c, false));
+        plans.push_back(sum_plan(req, spec, c.cnt[SERIES]));
+        const ChunkLayout &L = lay.back();
+        if (L.P < 1 || !chunk_pairs_agree(req, c, L) || L.P % c.cnt[SERIES] != 0 ||
+            L.P / c.cnt[SERIES] > HHMM_SUMMARY_MAX_DRAWS) {
+            set_error("internal: a summary range of %lld series describes %lld pairs", (long long)c.cnt[SERIES],
+                      (long long)L.P);
+            return HHMM_ERR_INVALID_ARGUMENT;
+        }
+        slot_bytes = std::max(slot_bytes, L.total);
+        in_bytes = std::max(in_bytes, L.in_end);
+        sum_bytes = std::max(sum_bytes, plans.back().total);
+        host_bytes = std::max(host_bytes, plans.back().total + (pair_arrays.size() * 8 + 4) * (size_t)L.P + 1024);
+        wsb = std::max(wsb, ws_of(c, L.P));
+    }
+    hipStream_t pst[3];
+    hhmm_status s = get_pipe_streams(dev, pst);
+    if (s != HHMM_OK)
+        return s;
+    const hipStream_t st = pst[1];
+    void *dslot = pool_get(dev, slot_bytes), *dsum = pool_get(dev, sum_bytes), *ws = pool_get(dev, wsb);
+    void *hin = host_get(in_bytes), *hout = host_get(host_bytes);
+    auto cleanup = [&]() {
+        pool_put(dslot);
+        pool_put(dsum);
+        pool_put(ws);
+        host_put(hin);
+        host_put(hout);
+    };
+    if (!dslot || !dsum || !ws || !hin || !hout) {
+        cleanup();
+        set_error("device %d: allocation of a summary range's buffers failed (%zu + %zu + %zu device, %zu + %zu "
+                  "pinned bytes)", dev, slot_bytes, sum_bytes, wsb, in_bytes, host_bytes);
+        return HHMM_ERR_OUT_OF_MEMORY;
+    }
+    const bool ragged = d.T != nullptr || d.T_oos != nullptr;
+    const size_t Q = (size_t)spec->n_probs;
+    /* the caller's summary arrays <-> the range's packed [Nc, ...] copies in hout */
+    auto move_summaries = [&](const Shard &c, const SumPlan &pl, bool to_host_arrays) {
+        const size_t Nc = (size_t)c.cnt[SERIES], a = (size_t)c.off[SERIES];
+        for (int b = 0; b < 32; ++b) {
+            if (!((spec->summarise >> b) & 1u))
+                continue;
+            const size_t rows = sum_T(req, b) * sum_K(req, b) * Q;
+            char *hq = (char *)(out->quantiles[b] + a), *pq = (char *)hout + pl.qoff[b];
+            if (to_host_arrays)
+                par_copy_rows(hq, (size_t)N * 8, pq, Nc * 8, Nc * 8, rows);
+            else
+                par_copy_rows(pq, Nc * 8, hq, (size_t)N * 8, Nc * 8, rows);
+            if ((spec->argmax >> b) & 1u) {
+                char *ha = (char *)(out->argmax[b] + a), *pa = (char *)hout + pl.aoff[b];
+                if (to_host_arrays)
+                    par_copy_rows(ha, (size_t)N * 4, pa, Nc * 4, Nc * 4, sum_T(req, b));
+                else
+                    par_copy_rows(pa, Nc * 4, ha, (size_t)N * 4, Nc * 4, sum_T(req, b));
+            }
+        }
+    };
+    int64_t fails = 0;
+    hhmm_status ls = HHMM_OK;
+    for (size_t i = 0; i < ranges.size(); ++i) {
+        const ChunkLayout &L = lay[i];
+        const SumPlan &pl = plans[i];
+        const Shard &c = ranges[i];
+        for (size_t j = 0; j < arrays.size(); ++j) {
+            if (L.off[j] >= L.in_end)
+                continue;
+            const ShardRows r = shard_rows(arrays[j].host, arrays[j], c);
+            par_copy_rows((char *)hin + L.off[j], r.width, r.base, r.pitch, r.width, r.rows);
+        }
+        if ((e = hipMemcpyAsync(dslot, hin, L.in_end, hipMemcpyHostToDevice, st)) != hipSuccess)
+            break;
+        if (ragged) { /* steps past a series' end keep the caller's fill: they travel up and back */
+            move_summaries(c, pl, false);
+            if ((e = hipMemcpyAsync(dsum, hout, pl.total, hipMemcpyHostToDevice, st)) != hipSuccess)
+                break;
+        }
+        if ((e = hipMemsetAsync((char *)dslot + L.status_off, 0, (size_t)L.P * sizeof(int32_t), st)) != hipSuccess)
+            break;
+        hhmm_request cr = dreq;
+        hhmm_result cq = dres;
+        cr.data.n_series = c.cnt[SERIES];
+        cr.draws.n_draws = c.cnt[DRAWS];
+        for (size_t j = 0; j < arrays.size(); ++j) { /* as run_on_device binds a chunk */
+            const char *slot_base = (const char *)arrays[j].dev_slot;
+            void **f = nullptr;
+            if (slot_base >= (const char *)&dreq && slot_base < (const char *)(&dreq + 1))
+                f = (void **)((char *)&cr + (slot_base - (const char *)&dreq));
+            else
+                f = (void **)((char *)&cq + (slot_base - (const char *)&dres));
+            *f = (char *)dslot + L.off[j];
+        }
+        cq.pair_status = (int32_t *)((char *)dslot + L.status_off);
+        if ((ls = launch_all(&cr, &cq, L.P, ws, st)) != HHMM_OK)
+            break;
+        for (int b = 0; b < 32 && ls == HHMM_OK; ++b) {
+            if (!((spec->summarise >> b) & 1u))
+                continue;
+            bool i32 = false;
+            const size_t fo = sum_field(b, i32);
+            hhmm_summary_request sr{};
+            sr.n_series = c.cnt[SERIES];
+            sr.n_draws = L.P / c.cnt[SERIES];
+            sr.T_max = (int32_t)sum_T(req, b);
+            sr.K = (int32_t)sum_K(req, b);
+            sr.T = sum_uses_oos(req, b) ? cr.data.T_oos : cr.data.T;
+            sr.n_probs = spec->n_probs;
+            memcpy(sr.probs, spec->probs, sizeof(sr.probs));
+            const bool arg = (spec->argmax >> b) & 1u;
+            sr.argmax_prob = arg ? spec->argmax_prob : -1.0;
+            void *vals = *(void **)((char *)&cq + fo);
+            if (i32)
+                sr.values_i32 = (const int32_t *)vals;
+            else
+                sr.values_f64 = (const double *)vals;
+            ls = launch_summary(&sr, (double *)((char *)dsum + pl.qoff[b]),
+                                arg ? (int32_t *)((char *)dsum + pl.aoff[b]) : nullptr, st);
+        }
+        if (ls != HHMM_OK)
+            break;
+        size_t ho = pl.total;
+        if ((e = hipMemcpyAsync(hout, dsum, pl.total, hipMemcpyDeviceToHost, st)) != hipSuccess)
+            break;
+        for (size_t j : pair_arrays) {
+            if ((e = hipMemcpyAsync((char *)hout + ho, (char *)dslot + L.off[j], (size_t)L.P * 8,
+                                    hipMemcpyDeviceToHost, st)) != hipSuccess)
+                break;
+            ho += (size_t)L.P * 8;
+        }
+        if (e != hipSuccess ||
+            (e = hipMemcpyAsync((char *)hout + ho, (char *)dslot + L.status_off, (size_t)L.P * 4,
+                                hipMemcpyDeviceToHost, st)) != hipSuccess ||
+            (e = sync_request(st)) != hipSuccess)
+            break;
+        move_summaries(c, pl, true);
+        ho = pl.total;
+        for (size_t j : pair_arrays) {
+            memcpy((char *)arrays[j].host + (size_t)c.off[PAIRS] * 8, (char *)hout + ho, (size_t)L.P * 8);
+            ho += (size_t)L.P * 8;
+        }
+        const int32_t *q = (const int32_t *)((char *)hout + ho);
+        memcpy(status + c.off[PAIRS], q, (size_t)L.P * 4);
+        for (int64_t p = 0; p < L.P; ++p)
+            fails += q[p] != 0;
+    }
+    if (ls != HHMM_OK || e != hipSuccess) {
+        const std::string first = hhmm_last_error();
+        const hipError_t dr = sync_request(st); /* nothing of this request still runs when its buffers are pooled again */
+        cleanup();
+        if (ls == HHMM_OK)
+            return hip_fail(e, "summary run (copy or kernel execution)");
+        if (dr != hipSuccess)
+            set_error("%s; draining the request's stream then failed: %s", first.c_str(), hipGetErrorString(dr));
+        return ls;
+    }
+    cleanup();
+    *failures = fails;
+    return HHMM_OK;
+}
+
+static hhmm_status run_summary(const hhmm_request *req, const hhmm_summary_spec *spec, hhmm_result *pairs,
+                               const hhmm_result *full, hhmm_summary_result *out)
+{
+    const int64_t P = npairs(req), N = req->data.n_series;
+    std::vector<int> devs;
+    if (req->device == HHMM_DEVICE_SET) {
+        std::lock_guard<std::mutex> g(devset().mu);
+        devs = devset().devs.empty() ? std::vector<int>{0} : devset().devs;
+    } else {
+        int dev = req->device;
+        if (dev < 0 && hipGetDevice(&dev) != hipSuccess)
+            return hip_fail(hipGetLastError(), "hipGetDevice");
+        devs.push_back(dev);
+    }
+    const size_t ns = (size_t)std::min<int64_t>(N, (int64_t)devs.size()); /* series ranges only, never draws */
+    std::vector<int32_t> status((size_t)P, 0);
+    std::vector<hhmm_status> st(ns, HHMM_OK);
+    std::vector<std::string> msg(ns);
+    std::vector<int64_t> fails(ns, 0);
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    auto work = [&](size_t i) {
+        const hipError_t e = hipSetDevice(devs[i]);
+        if (e != hipSuccess)
+            st[i] = hip_fail(e, "hipSetDevice");
+        else
+            st[i] = run_summary_on_device(req, spec, full, out, N * (int64_t)i / (int64_t)ns,
+                                          N * (int64_t)(i + 1) / (int64_t)ns, ns > 1, status.data(), &fails[i]);
+        if (st[i] != HHMM_OK)
+            msg[i] = hhmm_last_error();
+    };
+    std::vector<std::thread> th;
+    std::vector<size_t> mine{0};
+    for (size_t i = 1; i < ns; ++i) {
+        try {
+            th.emplace_back(work, i);
+        } catch (...) { /* no exception crosses the C ABI: this thread runs that range too */
+            mine.push_back(i);
+        }
+    }
+    for (size_t i : mine)
+        work(i);
+    for (auto &t : th)
+        t.join();
+    if (req->device == HHMM_DEVICE_SET)
+        (void)hipSetDevice(cur);
+    for (size_t i = 0; i < ns; ++i)
+        if (st[i] != HHMM_OK) {
+            if (ns > 1)
+                set_error("range %zu (device %d): %s", i, devs[i], msg[i].c_str());
+            else
+                set_error("%s", msg[i].c_str());
+            return st[i];
+        }
+    if (pairs && pairs->pair_status)
+        memcpy(pairs->pair_status, status.data(), (size_t)P * sizeof(int32_t));
+    int64_t failures = 0;
+    for (int64_t f : fails)
+        failures += f;
+    if (failures) {
+        set_error("%lld pair(s) hit an unset Viterbi back-pointer (Stan would throw)", (long long)failures);
+        return HHMM_WARN_PAIR_FAILURES;
+    }
+    return HHMM_OK;
+}
+
 } // namespace hhmm
 
 using namespace hhmm;
@@ -1358,6 +1749,65 @@ hhmm_status hhmm_run(const hhmm_request *req, hhmm_result *res)
         return HHMM_WARN_PAIR_FAILURES;
     }
     return HHMM_OK;
+}
+
+hhmm_status hhmm_run_summary(const hhmm_request *req, const hhmm_summary_spec *spec, hhmm_result *pairs,
+                             hhmm_summary_result *out)
+{
+    REQUIRE(req && spec && pairs && out, "request, spec, pairs and out must be non-NULL");
+    REQUIRE(req->pairing != HHMM_PAIR_ZIP, "hhmm_run_summary: ZIP pairing has one draw per series, nothing to reduce");
+    REQUIRE(spec->n_probs >= 1 && spec->n_probs <= HHMM_SUMMARY_MAX_PROBS, "summary needs 1 <= n_probs <= %d (got %d)",
+            HHMM_SUMMARY_MAX_PROBS, spec->n_probs);
+    for (int j = 0; j < spec->n_probs; ++j)
+        REQUIRE(spec->probs[j] >= 0.0 && spec->probs[j] <= 1.0, "summary probs[%d] = %g outside [0, 1]", j,
+                spec->probs[j]);
+    REQUIRE((spec->summarise & ~kSumStepBits) == 0, "summarise 0x%x holds bits that are no per-step output",
+            spec->summarise & ~kSumStepBits);
+    REQUIRE((req->outputs & kSumStepBits & ~spec->summarise) == 0,
+            "per-step outputs 0x%x are requested but not in spec->summarise (hhmm_run_summary returns no per-draw "
+            "array; use hhmm_run)", req->outputs & kSumStepBits & ~spec->summarise);
+    REQUIRE((spec->argmax & ~(spec->summarise & kSumKAxisBits)) == 0,
+            "argmax 0x%x must be a subset of summarise with a K axis", spec->argmax);
+    if (spec->argmax)
+        REQUIRE(spec->argmax_prob >= 0.0 && spec->argmax_prob <= 1.0, "summary argmax_prob = %g outside [0, 1]",
+                spec->argmax_prob);
+    for (int b = 0; b < 32; ++b) {
+        if ((spec->summarise >> b) & 1u)
+            REQUIRE(out->quantiles[b], "summary of output bit %d requested but out->quantiles[%d] is NULL", b, b);
+        if ((spec->argmax >> b) & 1u)
+            REQUIRE(out->argmax[b], "argmax of output bit %d requested but out->argmax[%d] is NULL", b, b);
+    }
+    hhmm_request r2 = *req;
+    r2.outputs |= spec->summarise;
+    /* what validate() and describe() see: the caller's [P] pointers, and for the
+     * per-step outputs (device-only here) a placeholder that is never dereferenced */
+    hhmm_result full{};
+    full.loglik = pairs->loglik;
+    full.logp_zstar = pairs->logp_zstar;
+    full.pair_status = pairs->pair_status;
+    static double placeholder;
+    for (int b = 0; b < 32; ++b) {
+        bool i32 = false;
+        const size_t fo = sum_field(b, i32);
+        if (((spec->summarise >> b) & 1u) && fo != (size_t)-1)
+            *(void **)((char *)&full + fo) = &placeholder;
+    }
+    hhmm_status s = validate(&r2, &full, true);
+    if (s != HHMM_OK)
+        return s;
+    const int64_t P = npairs(&r2), N = r2.data.n_series;
+    if (P / N > HHMM_SUMMARY_MAX_DRAWS) {
+        set_error("summary of S = %lld draws per series: at most %d (one cell is sorted in one workgroup's LDS)",
+                  (long long)(P / N), HHMM_SUMMARY_MAX_DRAWS);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if (!device_supported(r2.model)) {
+        set_error("model %d has no gfx950 path in this build", r2.model);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if ((s = check_device()) != HHMM_OK)
+        return s;
+    return run_summary(&r2, spec, pairs, &full, out);
 }
 
 int hhmm_device_set(int32_t *ordinals, int capacity)

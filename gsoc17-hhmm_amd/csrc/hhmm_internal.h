@@ -10,6 +10,7 @@
 
 #include "hhmm.h"
 #include "hhmm_features.h"
+#include "hhmm_summary.h"
 
 namespace hhmm {
 
@@ -208,6 +209,11 @@ hhmm_status join_stream(hipStream_t st, hipStream_t side);
 hhmm_status selftest_cr_math(const double *in, double *out, int64_t n, int which);
 
 void set_error(const char *fmt, ...);
+
+/* Reduction over draws (hhmm_summary.hip): argument checks (no device needed)
+ * and the launch on `st` (device pointers). */
+hhmm_status check_summary(const hhmm_summary_request *r, const double *quantiles, const int32_t *argmax);
+hhmm_status launch_summary(const hhmm_summary_request *r, double *quantiles, int32_t *argmax, hipStream_t st);
 
 /* Tick -> zig-zag -> leg feature extractor (hhmm_features.hip). */
 size_t features_workspace_bytes(int64_t n);

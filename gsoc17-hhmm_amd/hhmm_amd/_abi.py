@@ -169,6 +169,45 @@ class Result(C.Structure):
     ]
 
 
+# include/hhmm_summary.h
+SUMMARY_MAX_PROBS = 16
+SUMMARY_MAX_DRAWS = 16384
+
+
+class SummaryRequest(C.Structure):
+    _fields_ = [
+        ("n_series", C.c_int64),
+        ("n_draws", C.c_int64),
+        ("T_max", C.c_int32),
+        ("K", C.c_int32),
+        ("T", C.c_void_p),
+        ("n_probs", C.c_int32),
+        ("reserved", C.c_int32),
+        ("probs", C.c_double * SUMMARY_MAX_PROBS),
+        ("argmax_prob", C.c_double),
+        ("values_f64", C.c_void_p),
+        ("values_i32", C.c_void_p),
+    ]
+
+
+class SummarySpec(C.Structure):
+    _fields_ = [
+        ("n_probs", C.c_int32),
+        ("summarise", C.c_uint32),
+        ("argmax", C.c_uint32),
+        ("reserved", C.c_int32),
+        ("probs", C.c_double * SUMMARY_MAX_PROBS),
+        ("argmax_prob", C.c_double),
+    ]
+
+
+class SummaryResult(C.Structure):
+    _fields_ = [
+        ("quantiles", C.c_void_p * 32),
+        ("argmax", C.c_void_p * 32),
+    ]
+
+
 # Data-block fields (name -> (ctype kind, shape code)).  Shape codes use
 # N = series, T = T_max, M, To = T_oos_max.
 DATA_ARRAYS = {
@@ -260,4 +299,11 @@ def declare(lib):
     lib.hhmm_selftest_shards.restype = C.c_int
     lib.hhmm_selftest_pipeline.argtypes = [RP, SP, C.c_int, C.c_int]
     lib.hhmm_selftest_pipeline.restype = C.c_int
+    QP = C.POINTER(SummaryRequest)
+    lib.hhmm_summary.argtypes = [QP, C.c_void_p, C.c_void_p, C.c_int]
+    lib.hhmm_summary.restype = C.c_int
+    lib.hhmm_summary_device.argtypes = [QP, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.hhmm_summary_device.restype = C.c_int
+    lib.hhmm_run_summary.argtypes = [RP, C.POINTER(SummarySpec), SP, C.POINTER(SummaryResult)]
+    lib.hhmm_run_summary.restype = C.c_int
     return lib

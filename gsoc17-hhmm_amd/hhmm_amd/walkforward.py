@@ -18,7 +18,9 @@ Here the per-task steps map onto the engine:
                   evaluates window n under draw p), so one hhmm_run evaluates
                   all fits' generated quantities at once;
   split()         the batched outputs back into per-window extract()-shaped
-                  arrays ([B, T_n, K] / [B, T_n] / [B]).
+                  arrays ([B, T_n, K] / [B, T_n] / [B]);
+  filtered_states()  wf-trade.R:119-120 from hhmm_amd.gqs_summary's hard states:
+                  per window the in- and out-of-sample filtered state paths.
 """
 import pathlib
 
@@ -139,3 +141,19 @@ def split(result, data):
                 d[k] = v[sl, :steps]
         per.append(d)
     return per
+
+
+def filtered_states(summary, data):
+    """wf-trade.R:119-120 for every window of a batched request:
+        state.filtered.ins <- apply(apply(alpha_tk,     c(2, 3), median), 1, which.max)
+        state.filtered.oos <- apply(apply(alpha_tk_oos, c(2, 3), median), 1, which.max)
+    `summary` is gqs_summary(..., pars=[..., "alpha_tk", "alpha_tk_oos"],
+    hard=("alpha_tk", "alpha_tk_oos")) of the assemble()d request (argmax_prob
+    0.5, the median); returns one dict per window with the two 1-based state
+    paths over that window's own T_n / T_oos_n steps."""
+    T, To = np.asarray(data["T"]).reshape(-1), np.asarray(data["T_oos"]).reshape(-1)
+    ins, oos = np.asarray(summary["hard_alpha_tk"]), np.asarray(summary["hard_alpha_tk_oos"])
+    if ins.shape[0] != T.size or oos.shape[0] != To.size:
+        raise ValueError("summary and data describe different numbers of windows")
+    return [{"state.filtered.ins": ins[n, :T[n]].copy(), "state.filtered.oos": oos[n, :To[n]].copy()}
+            for n in range(T.size)]
