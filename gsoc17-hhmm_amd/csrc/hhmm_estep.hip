@@ -1,0 +1,516 @@
+/*
+ * hhmm_estep.hip -- gfx950 kernel of the batched E-step (include/hhmm_estep.h):
+ * per (series, draw) pair the expected sufficient statistics summed over the
+ * steps -- gamma_1, the pairwise posterior sum xi_ij and the emission sums --
+ * for hmm and hmm-multinom at K <= 8.  Nothing is written per step.
+ *
+ * One LANE owns one pair (hhmm_hmm.h's layout, helpers and latency rules).
+ *   forward   fb_kernel's scaled linear-space sweep (fwd_chunk): a checkpoint
+ *             of alpha every C = fb_chunk(K) steps, loglik at the end.
+ *   backward  chunk by chunk from the end: alpha over the chunk is recomputed
+ *             from its checkpoint, beta is carried.  The transition into step
+ *             t >= 2 takes alpha_{t-1}, so a chunk handles the transitions
+ *             into its steps 2..C and into the first step of the chunk after
+ *             it.  With b_t = e_t .* beta_t:
+ *                 beta_{t-1}(i) = sum_j A(i,j) b_t(j)
+ *                 Z             = sum_i alpha_{t-1}(i) beta_{t-1}(i)
+ *                 xi(i,j)      += alpha_{t-1}(i) A(i,j) b_t(j) / Z
+ *                 gamma_t(j)    = sum_i of the same terms
+ *             (A(i,j) is constant over t, so the accumulator takes it once, at
+ *             the end: K^2 FMAs per step; a zero in A stays an exact zero.)
+ *             One reciprocal per step: dividing by Z cancels every power-of-two
+ *             scale of alpha and beta, so no exponent is tracked backward.
+ *             gamma_1 = alpha_1 .* beta_1 / their sum.  A step with Z == 0 or
+ *             a non-finite Z, or a non-finite loglik, makes the pair's
+ *             statistics NaN.
+ * Accumulators: xi in K^2 fp64 registers (in LDS for the Gaussian kernels at
+ * K >= 7, estep_xi_lds); the Gaussian sums in 3K registers;
+ * c_kl in a second LDS slab per wave with the phi table's layout
+ * (slab[(l * KP + kp) * 64 + lane], double2), so the update of row x_t is the
+ * emission fetch's conflict-free 16-byte pattern.  Two slabs cost
+ * 2 L ceil(K/2) KiB per wave; the workgroup is sized to fit 160 KiB.
+ * The [P, ...] stores are pair-fastest: one coalesced wave transaction each.
+ */
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "hhmm_estep.h"
+#include "hhmm_hmm.h"
+
+namespace hhmm {
+
+struct EstepOut {
+    double *loglik, *n1, *xi, *c, *w, *s1, *s2;
+    int32_t *status;
+};
+
+/* xi lives in LDS instead of registers (xs[(i * K + j) * 64 + lane]) where the
+ * registers do not hold it: the Gaussian kernels at K >= 7, whose per-state
+ * constants and exp take the room (228 VGPR spills at K = 8 otherwise); they
+ * have no emission tables, so 4 waves * K^2 * 512 B <= 128 KiB is free. */
+template <int MODEL, int K>
+constexpr bool estep_xi_lds() { return ModelTraits<MODEL>::kGauss && K >= 7; }
+
+/* The transition into a step with emission e: accumulates xi (without its
+ * constant factor A) and returns the step's gamma in g; be: beta_t in,
+ * beta_{t-1} out.  Returns Z. */
+template <int MODEL, int K>
+__device__ __forceinline__ double estep_transition(const PairParams<MODEL, K> &pp, const double (&ap)[K],
+                                                   const double (&e)[K], double (&be)[K], double (&xi)[K][K],
+                                                   double *xs, double (&g)[K])
+{
+    double b[K], bn[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+        b[j] = e[j] * be[j];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        double acc = pp.A[i][0] * b[0];
+#pragma unroll
+        for (int j = 1; j < K; ++j)
+            acc = fma(pp.A[i][j], b[j], acc);
+        bn[i] = acc;
+    }
+    double Z = ap[0] * bn[0];
+#pragma unroll
+    for (int i = 1; i < K; ++i)
+        Z = fma(ap[i], bn[i], Z);
+    const double r = 1.0 / Z;
+    /* A is constant over the steps: xi accumulates alpha_{t-1}(i) b_t(j) / Z and
+     * takes its factor A(i,j) once, at the end (estep_kernel's stores) */
+    double apr[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+        apr[i] = ap[i] * r;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        double sj = apr[0] * pp.A[0][j];
+#pragma unroll
+        for (int i = 1; i < K; ++i)
+            sj = fma(apr[i], pp.A[i][j], sj);
+        g[j] = sj * b[j];
+    }
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if constexpr (estep_xi_lds<MODEL, K>())
+                xs[(i * K + j) * 64] = fma(apr[i], b[j], xs[(i * K + j) * 64]);
+            else
+                xi[i][j] = fma(apr[i], b[j], xi[i][j]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+        be[i] = bn[i];
+    int ex = 0;
+    renorm<K>(be, ex);
+    return Z;
+}
+
+/* gamma of one step into the emission sums: row x of the c_kl slab (clamped
+ * like the emission fetch), or the Gaussian moments. */
+template <int MODEL, int K>
+__device__ __forceinline__ void estep_emit_acc(double2 *cslab, int L, const Obs &o, const double (&g)[K],
+                                               double (&w)[K], double (&s1)[K], double (&s2)[K])
+{
+    if constexpr (ModelTraits<MODEL>::kGauss) {
+        const double x = o.xr, x2 = o.xr * o.xr;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            w[k] += g[k];
+            s1[k] = fma(g[k], x, s1[k]);
+            s2[k] = fma(g[k], x2, s2[k]);
+        }
+    } else {
+        constexpr int KP = (K + 1) / 2;
+        const int xc = min(max(o.x, 1), L);
+        double2 *r = (cslab - KP * 64) + xc * (KP * 64);
+#pragma unroll
+        for (int kp = 0; kp < KP; ++kp) {
+            double2 v = r[kp * 64];
+            v.x += g[2 * kp];
+            if (2 * kp + 1 < K)
+                v.y += g[2 * kp + 1];
+            r[kp * 64] = v;
+        }
+    }
+}
+
+template <int MODEL, int K>
+__global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const EstepOut o)
+{
+    constexpr int C = fb_chunk(K);
+    constexpr int KP = (K + 1) / 2;
+    constexpr bool GAUSS = ModelTraits<MODEL>::kGauss;
+    HIP_DYNAMIC_SHARED(double2, lds)
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int nw = blockDim.x >> 6;
+    const int64_t gwave = (int64_t)blockIdx.x * nw + wave;
+    /* lanes past the last pair redo pair P-1 (identical values, benign
+     * duplicate stores): every lane stays in the wave-wide reductions */
+    const int64_t p = min(gwave * 64 + lane, a.P - 1);
+    int64_t n, d;
+    pair_coords(a, p, n, d);
+
+    FbLane<MODEL, K> ln;
+    ln.p = p;
+    ln.n = n;
+    ln.L = a.L;
+    ln.t0 = 0;
+    ln.Tp = pair_len(a, n);
+    ln.cb = 0;
+    ln.q = p;
+    ln.Qs = a.P;
+    const size_t slab_elems = GAUSS ? 0 : (size_t)a.L * KP * 64;
+    double2 *const pslab = lds + (size_t)wave * slab_elems + lane;
+    double2 *const cslab = lds + (size_t)(nw + wave) * slab_elems + lane;
+    ln.slab = pslab;
+    load_params<MODEL, K, false>(ln.pp, a, d);
+    if constexpr (!GAUSS) {
+        fill_table<K, false>(pslab, a, d);
+        for (int i = 0; i < a.L * KP; ++i)
+            cslab[i * 64] = make_double2(0.0, 0.0);
+    }
+    constexpr bool XL = estep_xi_lds<MODEL, K>();
+    double *const xs = reinterpret_cast<double *>(lds) + (size_t)wave * (K * K * 64) + lane;
+    if constexpr (XL) {
+#pragma unroll
+        for (int i = 0; i < K * K; ++i)
+            xs[i * 64] = 0.0;
+    }
+    const SeriesPtrs sp = series_ptrs<MODEL, false>(a, n);
+    const int Tw_min = wave_min(ln.Tp);
+    const int Tw_max = wave_max(ln.Tp);
+    const int nfull = Tw_min / C;            /* chunks complete for every lane */
+    const int nchunk = (Tw_max + C - 1) / C; /* chunks any lane needs: <= ceil(Tmax / C) checkpoint rows */
+
+    /* ---- forward sweep: fb_kernel's, checkpoints only ---- */
+    double ll;
+    uint32_t xm = 0;
+    Obs cur[C];
+    {
+        double al[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            al[k] = 0.0;
+        double lsc = 0.0;
+        int ex = 0;
+        constexpr int D = kFwdGroup;
+        Obs grp[D][C];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+            load_chunk<MODEL, C, false>(grp[i], sp, i * C);
+        Em<K> ecur;
+        emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, grp[0][0], ecur);
+        int c = 0;
+        for (; c + D <= nfull; c += D) {
+            Obs nxt[D][C];
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+                load_chunk<MODEL, C, false>(nxt[i], sp, (c + D + i) * C);
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                fwd_chunk<MODEL, K, C, FB_GAMMA, true>(a, ln, c + i, grp[i],
+                                                       (i + 1 < D) ? grp[i + 1 < D ? i + 1 : 0][0] : nxt[0][0], ecur,
+                                                       al, lsc, ex);
+                if constexpr (!GAUSS)
+                    xcheck_acc<C, true>(xm, grp[i], c + i, ln.Tp);
+            }
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int u = 0; u < C; ++u)
+                    grp[i][u] = nxt[i][u];
+        }
+#pragma unroll
+        for (int u = 0; u < C; ++u)
+            cur[u] = grp[0][u];
+        for (; c < nchunk; ++c) {
+            Obs nxt[C];
+            load_chunk<MODEL, C, false>(nxt, sp, (c + 1) * C);
+            fwd_chunk<MODEL, K, C, FB_GAMMA, false>(a, ln, c, cur, nxt[0], ecur, al, lsc, ex);
+            if constexpr (!GAUSS)
+                xcheck_acc<C, false>(xm, cur, c, ln.Tp);
+#pragma unroll
+            for (int u = 0; u < C; ++u)
+                cur[u] = nxt[u];
+        }
+        ll = log(vsum<K>(al)) + (lsc + kLn2 * ex);
+    }
+
+    /* ---- backward sweep, chunk by chunk from the end ---- */
+    double xi[K][K], be[K], n1[K], w[K], s1[K], s2[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        be[i] = 1.0; /* beta_T uniform */
+        n1[i] = w[i] = s1[i] = s2[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            xi[i][j] = 0.0;
+    }
+    bool bad = !__builtin_isfinite(ll);
+    double x0 = 0.0;
+    const int clast = nchunk - 1;
+    load_chunk<MODEL, C, false>(cur, sp, clast * C);
+    /* checkpoint rows are wave-uniform: a lane shorter than the wave reads
+     * (unused) slots past its own last chunk, never past the allocation */
+    double ck[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        ck[k] = get_tmp(a.ckpt + a.P * ((int64_t)clast * K + k), (uint32_t)p * 8u);
+    Obs onext = cur[0];
+    for (int c = clast; c >= 0; --c) {
+        const int t0 = c * C;
+        Obs nxt[C];
+        load_chunk<MODEL, C, false>(nxt, sp, (c - 1) * C);
+        double cn[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            cn[k] = get_tmp(a.ckpt + a.P * ((int64_t)max(c - 1, 0) * K + k), (uint32_t)p * 8u);
+        /* alpha over the chunk from its checkpoint */
+        double abuf[C][K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            abuf[0][k] = ck[k];
+        {
+            int exb = 0;
+            Em<K> ecur;
+            emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, cur[1 < C ? 1 : 0], ecur);
+#pragma unroll
+            for (int u = 1; u < C; ++u) {
+                Em<K> enx;
+                emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, cur[u + 1 < C ? u + 1 : u], enx);
+                if (t0 + u < ln.Tp)
+                    fwd_step_to<MODEL, K>(abuf[u - 1], abuf[u], ln.pp, ecur.e, cur[u], exb);
+                ecur = enx;
+            }
+        }
+        /* transitions into steps t0 + C (the next chunk's first) .. t0 + 1 */
+        Em<K> ecur;
+        emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, onext, ecur);
+#pragma unroll
+        for (int v = C; v >= 1; --v) {
+            const Obs &ob = (v < C) ? cur[v < C ? v : 0] : onext;
+            Em<K> enx;
+            emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, cur[v - 1 >= 1 ? v - 1 : 1], enx);
+            if (t0 + v < ln.Tp) {
+                double g[K];
+                const double Z = estep_transition<MODEL, K>(ln.pp, abuf[v - 1], ecur.e, be, xi, xs, g);
+                bad |= !((Z > 0.0) & (Z < __builtin_inf()));
+                estep_emit_acc<MODEL, K>(cslab, a.L, ob, g, w, s1, s2);
+            }
+            ecur = enx;
+        }
+        if (c == 0) { /* the first step: gamma_1 = alpha_1 .* beta_1 / their sum */
+            double Z = 0.0;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                n1[k] = abuf[0][k] * be[k];
+                Z += n1[k];
+            }
+            const double r = 1.0 / Z;
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                n1[k] *= r;
+            bad |= !((Z > 0.0) & (Z < __builtin_inf()));
+            if constexpr (GAUSS) /* Q2: x_1 counts with weight 1 for every state */
+                x0 = cur[0].xr;
+            else
+                estep_emit_acc<MODEL, K>(cslab, a.L, cur[0], n1, w, s1, s2);
+        }
+        onext = cur[0];
+#pragma unroll
+        for (int u = 0; u < C; ++u)
+            cur[u] = nxt[u];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            ck[k] = cn[k];
+    }
+
+    /* ---- the [P, ...] outputs ---- */
+    const uint32_t po = (uint32_t)p * 8u;
+    const double nanv = dev_nan();
+    put_out(o.loglik, po, ll);
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        put_out(o.n1 + a.P * (int64_t)k, po, bad ? nanv : n1[k]);
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+#pragma unroll
+        for (int i = 0; i < K; ++i)
+            put_out(o.xi + a.P * (int64_t)(i + K * j), po,
+                    bad ? nanv : ln.pp.A[i][j] * (XL ? xs[(i * K + j) * 64] : xi[i][j]));
+    if constexpr (GAUSS) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            put_out(o.w + a.P * (int64_t)k, po, bad ? nanv : 1.0 + w[k]);
+            put_out(o.s1 + a.P * (int64_t)k, po, bad ? nanv : x0 + s1[k]);
+            put_out(o.s2 + a.P * (int64_t)k, po, bad ? nanv : x0 * x0 + s2[k]);
+        }
+    } else {
+        for (int l = 0; l < a.L; ++l) {
+#pragma unroll
+            for (int kp = 0; kp < KP; ++kp) {
+                const double2 v = cslab[(l * KP + kp) * 64];
+                put_out(o.c + a.P * ((int64_t)(2 * kp) + (int64_t)K * l), po, bad ? nanv : v.x);
+                if (2 * kp + 1 < K)
+                    put_out(o.c + a.P * ((int64_t)(2 * kp + 1) + (int64_t)K * l), po, bad ? nanv : v.y);
+            }
+        }
+    }
+    if (o.status) {
+        bool inv = !GAUSS && xm >= (uint32_t)a.L;
+        if (a.T)
+            inv |= a.T[n] < 1 || a.T[n] > a.Tmax;
+        o.status[p] = inv ? HHMM_PAIR_INVALID_DATA : HHMM_PAIR_OK;
+    }
+}
+
+/* Waves per workgroup and its LDS: two slabs per wave for hmm-multinom. */
+static int estep_waves(int model, int K, int L, size_t *lds)
+{
+    *lds = 0;
+    if (model == HHMM_MODEL_HMM_GAUSS) { /* K >= 7: xi in LDS (estep_xi_lds) */
+        *lds = K >= 7 ? (size_t)(kBlock / 64) * K * K * 64 * sizeof(double) : 0;
+        return kBlock / 64;
+    }
+    const size_t per_wave = 2 * (size_t)L * (size_t)((K + 1) / 2) * 64 * sizeof(double2);
+    int waves = kBlock / 64;
+    while (waves > 0 && per_wave * waves > kLdsLimit)
+        --waves;
+    *lds = per_wave * waves;
+    return waves;
+}
+
+static int64_t estep_chunks(int K, int Tmax) { return ((int64_t)Tmax + fb_chunk(K) - 1) / fb_chunk(K); }
+
+size_t estep_workspace_bytes(int K, int Tmax, int64_t P)
+{
+    return (size_t)estep_chunks(K, Tmax) * (size_t)K * (size_t)P * sizeof(double);
+}
+
+hhmm_status check_estep(const hhmm_request *r, const hhmm_estep_result *o)
+{
+    if (!r) {
+        set_error("request must be non-NULL");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (r->abi_version != HHMM_ABI_VERSION) {
+        set_error("abi_version %u != %u", r->abi_version, HHMM_ABI_VERSION);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (r->model < 1 || r->model > 9) {
+        set_error("unknown model id %d", r->model);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (r->model != HHMM_MODEL_HMM_GAUSS && r->model != HHMM_MODEL_HMM_MULTINOM) {
+        set_error("E-step: model %d is not supported (hmm and hmm-multinom only; the semisup and Tayal backward "
+                  "passes are not the adjoint of their forward)",
+                  r->model);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if (r->data.K > kMaxK) {
+        set_error("E-step: K = %d, the lane-per-pair kernel supports K <= %d", r->data.K, kMaxK);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if (r->device == HHMM_DEVICE_SET) {
+        set_error("E-step: HHMM_DEVICE_SET is not supported (one device per call)");
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if (r->model == HHMM_MODEL_HMM_MULTINOM && r->data.K >= 1 && r->data.L >= 1) {
+        size_t lds;
+        if (estep_waves(r->model, r->data.K, r->data.L, &lds) < 1) {
+            set_error("E-step: L * ceil(K / 2) = %d * %d > 80: the emission table and its count table of one wave "
+                      "do not fit in LDS",
+                      r->data.L, (r->data.K + 1) / 2);
+            return HHMM_ERR_UNSUPPORTED;
+        }
+    }
+    if (!o) {
+        set_error("E-step result must be non-NULL");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (!o->loglik || !o->n_1k || !o->xi_ij) {
+        set_error("E-step: loglik, n_1k and xi_ij must be non-NULL");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (r->model == HHMM_MODEL_HMM_MULTINOM && !o->c_kl) {
+        set_error("E-step: hmm-multinom needs c_kl");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (r->model == HHMM_MODEL_HMM_GAUSS && (!o->w_k || !o->s1_k || !o->s2_k)) {
+        set_error("E-step: hmm needs w_k, s1_k and s2_k");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    return HHMM_OK;
+}
+
+template <int MODEL, int K>
+static void launch_estep_k(const DevArgs &a, const EstepOut &o, dim3 grid, dim3 block, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((estep_kernel<MODEL, K>), grid, block, lds, st, a, o);
+}
+
+template <int MODEL>
+static bool launch_estep_m(const DevArgs &a, const EstepOut &o, dim3 grid, dim3 block, size_t lds, hipStream_t st)
+{
+    switch (a.K) {
+    case 1: launch_estep_k<MODEL, 1>(a, o, grid, block, lds, st); return true;
+    case 2: launch_estep_k<MODEL, 2>(a, o, grid, block, lds, st); return true;
+    case 3: launch_estep_k<MODEL, 3>(a, o, grid, block, lds, st); return true;
+    case 4: launch_estep_k<MODEL, 4>(a, o, grid, block, lds, st); return true;
+    case 5: launch_estep_k<MODEL, 5>(a, o, grid, block, lds, st); return true;
+    case 6: launch_estep_k<MODEL, 6>(a, o, grid, block, lds, st); return true;
+    case 7: launch_estep_k<MODEL, 7>(a, o, grid, block, lds, st); return true;
+    case 8: launch_estep_k<MODEL, 8>(a, o, grid, block, lds, st); return true;
+    default: return false;
+    }
+}
+
+hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws, hipStream_t st)
+{
+    DevArgs a{};
+    a.P = P;
+    a.N = r->data.n_series;
+    a.S = r->draws.n_draws;
+    a.pairing = r->pairing;
+    a.model = r->model;
+    a.K = r->data.K;
+    a.L = r->data.L;
+    a.Tmax = r->data.T_max;
+    a.Tout = r->data.T_max;
+    a.T = r->data.T;
+    a.x = r->data.x_int;
+    a.xr = r->data.x_real;
+    a.p_1k = r->draws.p_1k;
+    a.A_ij = r->draws.A_ij;
+    a.phi_k = r->draws.phi_k;
+    a.mu_k = r->draws.mu_k;
+    a.sigma_k = r->draws.sigma_k;
+    a.ckpt = (double *)ws;
+    EstepOut o{res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->w_k, res->s1_k, res->s2_k, res->pair_status};
+    size_t lds = 0;
+    const int waves = estep_waves(a.model, a.K, a.L, &lds);
+    if (waves < 1) {
+        set_error("E-step: the tables of K*L = %d*%d do not fit in LDS", a.K, a.L);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    const int threads = 64 * waves;
+    const dim3 grid((unsigned)((P + threads - 1) / threads)), block(threads);
+    const bool ok = a.model == HHMM_MODEL_HMM_GAUSS ? launch_estep_m<HHMM_MODEL_HMM_GAUSS>(a, o, grid, block, lds, st)
+                                                    : launch_estep_m<HHMM_MODEL_HMM_MULTINOM>(a, o, grid, block, lds, st);
+    if (!ok) {
+        set_error("E-step: K = %d outside 1..%d", a.K, kMaxK);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error("estep_kernel launch: %s", hipGetErrorString(e));
+        return HHMM_ERR_HIP;
+    }
+    return HHMM_OK;
+}
+
+} // namespace hhmm

@@ -11,6 +11,7 @@
 #include "hhmm.h"
 #include "hhmm_features.h"
 #include "hhmm_summary.h"
+#include "hhmm_estep.h"
 
 namespace hhmm {
 
@@ -214,6 +215,12 @@ void set_error(const char *fmt, ...);
  * and the launch on `st` (device pointers). */
 hhmm_status check_summary(const hhmm_summary_request *r, const double *quantiles, const int32_t *argmax);
 hhmm_status launch_summary(const hhmm_summary_request *r, double *quantiles, int32_t *argmax, hipStream_t st);
+
+/* Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
+ * checkpoint workspace and the launch on `st` (device pointers). */
+hhmm_status check_estep(const hhmm_request *r, const hhmm_estep_result *o);
+size_t estep_workspace_bytes(int K, int Tmax, int64_t P);
+hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws, hipStream_t st);
 
 /* Tick -> zig-zag -> leg feature extractor (hhmm_features.hip). */
 size_t features_workspace_bytes(int64_t n);

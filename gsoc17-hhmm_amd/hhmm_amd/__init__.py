@@ -11,5 +11,7 @@ bench.py.
 from . import _abi  # noqa: F401
 from .api import HHMMError, PreparedRequest, gqs, load_library, reshape_pairs  # noqa: F401
 from .summary import gqs_summary, quantiles  # noqa: F401
+from .estep import estep, m_step, score  # noqa: F401
+from .em import baum_welch  # noqa: F401
 
 __version__ = "0.1.0"

@@ -208,6 +208,20 @@ class SummaryResult(C.Structure):
     ]
 
 
+# include/hhmm_estep.h
+class EstepResult(C.Structure):
+    _fields_ = [
+        ("loglik", C.c_void_p),
+        ("n_1k", C.c_void_p),
+        ("xi_ij", C.c_void_p),
+        ("c_kl", C.c_void_p),
+        ("w_k", C.c_void_p),
+        ("s1_k", C.c_void_p),
+        ("s2_k", C.c_void_p),
+        ("pair_status", C.c_void_p),
+    ]
+
+
 # Data-block fields (name -> (ctype kind, shape code)).  Shape codes use
 # N = series, T = T_max, M, To = T_oos_max.
 DATA_ARRAYS = {
@@ -306,4 +320,11 @@ def declare(lib):
     lib.hhmm_summary_device.restype = C.c_int
     lib.hhmm_run_summary.argtypes = [RP, C.POINTER(SummarySpec), SP, C.POINTER(SummaryResult)]
     lib.hhmm_run_summary.restype = C.c_int
+    EP = C.POINTER(EstepResult)
+    lib.hhmm_estep_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
+    lib.hhmm_estep_workspace_size.restype = C.c_int
+    lib.hhmm_estep_device.argtypes = [RP, EP, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.hhmm_estep_device.restype = C.c_int
+    lib.hhmm_estep.argtypes = [RP, EP]
+    lib.hhmm_estep.restype = C.c_int
     return lib

@@ -1,0 +1,147 @@
+"""Batched E-step on the GPU (include/hhmm_estep.h) and what follows from it.
+
+`estep()` returns, per (series, draw) pair, the expected sufficient statistics
+of the HMM summed over the steps: gamma_1, the pairwise posterior sum xi_ij and
+the emission sums.  Nothing [P, T, K]-sized leaves the device.  Two things the
+reference's drivers lack are plain arithmetic on these [P, K..] arrays:
+
+  score()   the gradient of the model-block log-likelihood with respect to
+            every constrained parameter (Fisher's identity) -- what Stan's
+            autodiff recomputes inside NUTS on every leapfrog step;
+  m_step()  one Baum-Welch update (hhmm_amd.em.baum_welch iterates it).
+
+The statistics follow the CODED likelihood of each Stan program: hmm.stan:30
+adds sum_k normal_lpdf(x_1 | mu_k, sigma_k) to every state at t = 1 (quirk Q2),
+so x_1 enters w_k / s1_k / s2_k with weight 1 for every state.  hmm and
+hmm-multinom at K <= 8.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from .api import HHMMError, PreparedRequest, load_library
+
+MODELS = ("hmm", "hmm-multinom")
+_TINY = 1e-300
+
+
+def stat_shapes(model, P, K, L):
+    """{name: shape} of the statistics estep() returns for `model`."""
+    shapes = {"loglik": (P,), "n_1k": (P, K), "xi_ij": (P, K, K)}
+    if model == "hmm-multinom":
+        shapes["c_kl"] = (P, K, L)
+    else:
+        shapes.update({"w_k": (P, K), "s1_k": (P, K), "s2_k": (P, K)})
+    return shapes
+
+
+def prepare(model, data, draws, pairing="grid", device=-1):
+    """(PreparedRequest, EstepResult, {name: array}) with the shape checks."""
+    if model not in MODELS:
+        raise ValueError(f"the E-step covers {MODELS}, not {model!r}")
+    pr = PreparedRequest(model, data, draws, [], pairing, device)
+    if pairing == "zip" and pr.N != pr.S:
+        raise ValueError(f"zip pairing needs n_series ({pr.N}) == n_draws ({pr.S})")
+    L = int(data.get("L", 0))
+    need = ("p_1k", "A_ij", "phi_k") if model == "hmm-multinom" else ("p_1k", "A_ij", "mu_k", "sigma_k")
+    want = {"p_1k": (pr.S, pr.K), "A_ij": (pr.S, pr.K, pr.K), "phi_k": (pr.S, pr.K, L), "mu_k": (pr.S, pr.K),
+            "sigma_k": (pr.S, pr.K)}
+    for name in need:
+        if name not in draws:
+            raise ValueError(f"{model} needs the draw array {name}")
+        if np.shape(draws[name]) != want[name]:
+            raise ValueError(f"{name} must have shape {want[name]}, got {np.shape(draws[name])}")
+    res = _abi.EstepResult()
+    out = {}
+    for name, shape in stat_shapes(model, pr.P, pr.K, L).items():
+        out[name] = np.full(shape, np.nan, dtype=np.float64, order="F")
+        setattr(res, name, out[name].ctypes.data)
+    res.pair_status = pr.status.ctypes.data
+    return pr, res, out
+
+
+def estep(model, data, draws, pairing="grid", device=-1, lib=None, return_status=False):
+    """Expected sufficient statistics of every (series, draw) pair.
+
+    Returns {name: array}: loglik (P,), n_1k (P, K), xi_ij (P, K, K) and c_kl
+    (P, K, L) for hmm-multinom or w_k, s1_k, s2_k (P, K) for hmm.  A pair whose
+    log-likelihood is -inf or NaN has NaN statistics."""
+    lib = lib or load_library()
+    pr, res, out = prepare(model, data, draws, pairing, device)
+    st = lib.hhmm_estep(C.byref(pr.req), C.byref(res))
+    if st < 0:
+        raise HHMMError(st, lib.hhmm_last_error().decode())
+    if return_status:
+        out["pair_status"] = pr.status
+        out["status"] = st
+    return out
+
+
+def pair_draw(pairing, P, S, N):
+    """The draw index of every pair (include/hhmm.h, "Pairing")."""
+    p = np.arange(P)
+    return p % S if pairing == "grid" else p
+
+
+def _ratio(count, par):
+    """count / par with 0 / 0 -> 0 (a structural zero has no count and no score)."""
+    count, par = np.broadcast_arrays(np.asarray(count, dtype=np.float64), np.asarray(par, dtype=np.float64))
+    out = np.zeros(count.shape)
+    both0 = (count == 0) & (par == 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        np.divide(count, par, out=out, where=~both0)
+    return out
+
+
+def score(model, draws, stats, pairing, S, N):
+    """Gradient of loglik with respect to the constrained parameters, per pair.
+
+    {name: (P, ...)} for p_1k, A_ij and phi_k (hmm-multinom) or mu_k, sigma_k
+    (hmm), by Fisher's identity from the statistics of estep().  The simplex
+    parameters are treated as free coordinates: a directional derivative along
+    a tangent of the simplex is the matching difference of entries."""
+    if model not in MODELS:
+        raise ValueError(f"the E-step covers {MODELS}, not {model!r}")
+    P = stats["loglik"].shape[0]
+    d = pair_draw(pairing, P, S, N)
+    g = {"p_1k": _ratio(stats["n_1k"], np.asarray(draws["p_1k"])[d]),
+         "A_ij": _ratio(stats["xi_ij"], np.asarray(draws["A_ij"])[d])}
+    if model == "hmm-multinom":
+        g["phi_k"] = _ratio(stats["c_kl"], np.asarray(draws["phi_k"])[d])
+    else:
+        mu, sg = np.asarray(draws["mu_k"])[d], np.asarray(draws["sigma_k"])[d]
+        w, s1, s2 = stats["w_k"], stats["s1_k"], stats["s2_k"]
+        g["mu_k"] = (s1 - mu * w) / sg ** 2
+        g["sigma_k"] = -w / sg + (s2 - 2 * mu * s1 + mu ** 2 * w) / sg ** 3
+    return g
+
+
+def _rows(counts, prev):
+    """Counts over their row sums (last axis); a row whose sum is 0 keeps prev."""
+    tot = counts.sum(axis=-1, keepdims=True)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        new = counts / tot
+    return np.where(tot > 0, new, prev)
+
+
+def m_step(model, stats, prev=None):
+    """One Baum-Welch update from the statistics of estep(): per-pair parameters.
+
+    p_1k = n_1k; rows of A and phi are counts over their row sums (a row whose
+    sum is 0 keeps its value in `prev`, {name: (P, ...)}); mu = s1 / w;
+    sigma = sqrt(max(s2 / w - mu^2, tiny))."""
+    if model not in MODELS:
+        raise ValueError(f"the E-step covers {MODELS}, not {model!r}")
+    xi = stats["xi_ij"]
+    pa = prev["A_ij"] if prev is not None else np.full(xi.shape, np.nan)
+    new = {"p_1k": np.array(stats["n_1k"]), "A_ij": _rows(xi, pa)}
+    if model == "hmm-multinom":
+        c = stats["c_kl"]
+        new["phi_k"] = _rows(c, prev["phi_k"] if prev is not None else np.full(c.shape, np.nan))
+    else:
+        w = stats["w_k"]
+        mu = stats["s1_k"] / w
+        new["mu_k"] = mu
+        new["sigma_k"] = np.sqrt(np.maximum(stats["s2_k"] / w - mu ** 2, _TINY))
+    return new

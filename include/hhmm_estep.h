@@ -1,0 +1,80 @@
+/*
+ * hhmm_estep.h -- batched E-step of libhhmm.so: the expected sufficient
+ * statistics of an HMM, summed over the steps of every (series, draw) pair.
+ *
+ * Every output of include/hhmm.h is per step ([P, T, K] at the least).  A
+ * caller that improves a set of parameters instead of inspecting them needs
+ * the sums over t, and the pairwise posterior that no per-step output carries:
+ *
+ *   loglik [P]        l, the model-block log-likelihood (HHMM_OUT_LOGLIK)
+ *   n_1k   [P, K]     gamma_1(k)
+ *   xi_ij  [P, K, K]  sum_{t=2..T} P(z_{t-1} = i, z_t = j | x) at p + P*(i + K*j);
+ *                     all zero at T = 1
+ *   c_kl   [P, K, L]  hmm-multinom: sum_{t=1..T} gamma_t(k) [x_t = l]
+ *   w_k, s1_k, s2_k [P, K]  hmm: 1 + sum_{t>=2} gamma_t(k),
+ *                     x_1 + sum_{t>=2} gamma_t(k) x_t, x_1^2 + sum_{t>=2} gamma_t(k) x_t^2
+ *
+ * gamma and xi are the posteriors under the CODED likelihood of the Stan
+ * program.  hmm.stan:30 adds sum_k normal_lpdf(x_1 | mu_k, sigma_k) to every
+ * state at t = 1 (quirk Q2 of SURVEY.md App. A), so x_1 enters the Gaussian
+ * statistics with weight 1 for every state, not gamma_1(k); with that weight
+ * the usual formulas are the exact score of l (Fisher's identity):
+ *   dl/dmu_k    = (s1 - mu w) / sigma^2
+ *   dl/dsigma_k = -w / sigma + (s2 - 2 mu s1 + mu^2 w) / sigma^3
+ *   dl/dp_1k[k] = n_1k / p_1k    dl/dA_ij = xi_ij / A_ij    dl/dphi_kl = c_kl / phi_kl
+ *
+ * All outputs are fp64, pair-fastest ([P, ...] at p + P*(...)), tolerance 1e-9
+ * relative to max(1, |value|).  When l is -inf or NaN (an impossible
+ * observation, NaN draws) every statistic of the pair is NaN and pair_status
+ * stays HHMM_PAIR_OK.
+ *
+ * Scope: hmm and hmm-multinom at 1 <= K <= 8, every pairing, ragged T.  Other
+ * models, K > 8, HHMM_DEVICE_SET and an emission table with L * ceil(K / 2) >
+ * 80 (two tables of one wave do not fit a CU's LDS) answer HHMM_ERR_UNSUPPORTED.
+ * The request is the hhmm_request of hhmm.h; outputs, ffbs_u, hat_rand and the
+ * scan flags are ignored (the E-step is sequential in T per pair).
+ */
+#ifndef HHMM_ESTEP_H
+#define HHMM_ESTEP_H
+
+#include "hhmm.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Caller-allocated outputs.  The emission pointers of the other model may be
+ * NULL (c_kl for hmm; w_k, s1_k, s2_k for hmm-multinom); pair_status is optional. */
+typedef struct hhmm_estep_result {
+    double  *loglik;           /* [P] */
+    double  *n_1k;             /* [P, K] */
+    double  *xi_ij;            /* [P, K, K] */
+    double  *c_kl;             /* [P, K, L]  hmm-multinom */
+    double  *w_k;              /* [P, K]     hmm */
+    double  *s1_k;             /* [P, K]     hmm */
+    double  *s2_k;             /* [P, K]     hmm */
+    int32_t *pair_status;      /* [P] optional */
+} hhmm_estep_result;
+
+/* Bytes of device workspace hhmm_estep_device needs (the forward checkpoints). */
+hhmm_status hhmm_estep_workspace_size(const hhmm_request *req, size_t *bytes);
+
+/* Device-resident entry: every pointer in req / res is a device pointer on the
+ * current HIP device; enqueues on `stream` and returns without synchronising.
+ * A pair whose series breaks a data-block bound (x outside 1..L, T[n] outside
+ * 1..T_max) is flagged HHMM_PAIR_INVALID_DATA when pair_status is given (its
+ * statistics are unspecified; the table is never indexed with the bad symbol);
+ * every other pair is unaffected. */
+hhmm_status hhmm_estep_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+/* Host-pointer entry: validates the data block as hhmm_run does (a violation
+ * rejects the request), uploads, runs on req->device (-1 = current), downloads
+ * and synchronises. */
+hhmm_status hhmm_estep(const hhmm_request *req, hhmm_estep_result *res);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* HHMM_ESTEP_H */
