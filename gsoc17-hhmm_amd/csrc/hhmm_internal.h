@@ -12,6 +12,7 @@
 #include "hhmm_features.h"
 #include "hhmm_summary.h"
 #include "hhmm_estep.h"
+#include "hhmm_gibbs.h"
 
 namespace hhmm {
 
@@ -221,6 +222,12 @@ hhmm_status launch_summary(const hhmm_summary_request *r, double *quantiles, int
 hhmm_status check_estep(const hhmm_request *r, const hhmm_estep_result *o);
 size_t estep_workspace_bytes(int K, int Tmax, int64_t P);
 hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws, hipStream_t st);
+
+/* Draw statistics (hhmm_draw_stats.hip): argument checks (no device needed)
+ * and the launch on `st` (device pointers); the workspace is the E-step's. */
+hhmm_status check_draw_stats(const hhmm_request *r, const hhmm_estep_result *o);
+hhmm_status launch_draw_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
+                              hipStream_t st);
 
 /* Tick -> zig-zag -> leg feature extractor (hhmm_features.hip). */
 size_t features_workspace_bytes(int64_t n);

@@ -13,5 +13,6 @@ from .api import HHMMError, PreparedRequest, gqs, load_library, reshape_pairs  #
 from .summary import gqs_summary, quantiles  # noqa: F401
 from .estep import estep, m_step, score  # noqa: F401
 from .em import baum_welch  # noqa: F401
+from .gibbs import conditional_draw, draw_stats, gibbs, stack_chains  # noqa: F401
 
 __version__ = "0.1.0"
