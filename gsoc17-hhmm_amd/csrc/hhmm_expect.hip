@@ -1,0 +1,566 @@
+/*
+ * hhmm_expect.hip -- gfx950 kernel of the expected draw statistics
+ * (include/hhmm_expect.h): per (series, draw) pair the posterior expectation,
+ * under the coded path weight, of the counts hhmm_gibbs.h tabulates -- the
+ * E-step of hmm-multinom-semisup and hhmm-tayal2009 at K <= 8.  Nothing is
+ * written per step.  hmm-multinom has no mask and goes to launch_estep.
+ *
+ * estep_kernel's schedule (hhmm_estep.hip) with the auxiliary stream (g / sign)
+ * loaded beside x: one LANE per pair, a checkpoint of alpha every
+ * C = fb_chunk(K) steps from the forward sweep the engine already runs
+ * (fwd_chunk applies the masks), the chunk recomputed backward, xi in K^2
+ * registers, c_kl in a second LDS slab per wave.  The new piece is the ADJOINT
+ * of the masked forward step (bwd_step is the programs' own backward pass, which
+ * is not: semisup's is unmasked, Tayal's masks on the previous state).  With
+ * on(j) the forward mask of step t at state j and b = e_t .* beta_t:
+ *     beta_{t-1}(i) = sum_{j on} A(i,j) b(j) + sum_{j off} b(j)
+ *     Z             = sum_i alpha_{t-1}(i) beta_{t-1}(i),   a = alpha_{t-1} / Z
+ *     gamma_t(j)    = b(j) (on(j) ? sum_i a(i) A(i,j) : sum_i a(i))
+ *     xi(i,j)      += on(j) ? a(i) b(j) : 0
+ * xi takes its factor A(i,j) once, at the end: an "on" column always uses the
+ * constant A(i,j), so the deferred factor stays valid and a zero of A stays an
+ * exact zero.
+ * Tayal: where every lane of the wave has the step's sign (one series under
+ * many draws) the masks are compile-time constants (tayal_dispatch) and the
+ * structural zeros of A are skipped -- only under skip_ok, see tayal_nz.  Those
+ * arms do the per-lane form's additions in its order (what they skip are exact
+ * zeros), so a pair's bits do not depend on the other lanes of its wave.  The
+ * recompute of a chunk takes the masks per lane (fwd_step_raw: the same bits
+ * again): tayal_dispatch's arms cut every unrolled step into basic blocks.
+ */
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include "hhmm_expect.h"
+#include "hhmm_hmm.h"
+
+namespace hhmm {
+
+struct ExpectOut {
+    double *loglik, *n1, *xi, *c;
+    int32_t *status;
+    int32_t ahi; /* the auxiliary stream's upper bound: G (semisup), 2 (Tayal) */
+};
+
+/* beta_{t-1}(i) under per-lane masks, in the split form -- b divided by the
+ * mask once per step, then K FMAs per row: 2K selects -- or with a select per
+ * term (K^2 selects, K^2 extra adds).  The K >= 6 instances are past 256 VGPRs
+ * and keep the select form: with the split form hipcc's allocation of them
+ * left a dword in a private segment, which no instance may have. */
+constexpr bool expect_split(int K) { return K <= 5; }
+
+/* The adjoint transition into a step with emission e and observation o:
+ * accumulates xi (without its constant factor A) and returns the step's gamma
+ * in g; be: beta_t in, beta_{t-1} out.  Returns Z.  SG: the step's Tayal sign
+ * class when the wave shares it (tayal_dispatch), else -1 (the masks per lane). */
+template <int MODEL, int K, int SG>
+__device__ __forceinline__ double expect_transition(const PairParams<MODEL, K> &pp, const double (&ap)[K],
+                                                    const double (&e)[K], const Obs &o, double (&be)[K],
+                                                    double (&xi)[K][K], double (&g)[K])
+{
+    constexpr bool KNOWN = SG > 0 && ModelTraits<MODEL>::kTayal;
+    double b[K], bn[K];
+    bool on[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        b[j] = e[j] * be[j];
+        if constexpr (KNOWN)
+            on[j] = tayal_on(SG, j);
+        else if constexpr (ModelTraits<MODEL>::kSemisup)
+            on[j] = semisup_mask(o.aux, j);
+        else
+            on[j] = tayal_pred(o.aux, j);
+    }
+    if constexpr (KNOWN) {
+        /* the split form with the masks known: the same additions in the same
+         * order (the per-lane form's other terms are exact zeros) -- the same
+         * bits, so a pair's result does not depend on its wave's other lanes */
+        static_assert(expect_split(K), "the sign-class arms mirror the split form");
+        double boff = 0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (!on[j])
+                boff += b[j];
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            double acc = boff;
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (on[j] && tayal_nz(i, j < 4 ? j : 0))
+                    acc = fma(pp.A[i][j], b[j], acc);
+            bn[i] = acc;
+        }
+    } else if constexpr (expect_split(K)) {
+        /* b split by the mask: the "on" part takes A, the "off" part is one scalar */
+        double bon[K], boff = 0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            bon[j] = on[j] ? b[j] : 0.0;
+            boff += on[j] ? 0.0 : b[j];
+        }
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            double acc = fma(pp.A[i][0], bon[0], boff);
+#pragma unroll
+            for (int j = 1; j < K; ++j)
+                acc = fma(pp.A[i][j], bon[j], acc);
+            bn[i] = acc;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            double acc = 0.0;
+            bool first = true;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const double t = first ? pp.A[i][j] * b[j] : fma(pp.A[i][j], b[j], acc);
+                const double u = first ? b[j] : acc + b[j];
+                acc = on[j] ? t : u;
+                first = false;
+            }
+            bn[i] = acc;
+        }
+    }
+    double Z = ap[0] * bn[0];
+#pragma unroll
+    for (int i = 1; i < K; ++i)
+        Z = fma(ap[i], bn[i], Z);
+    const double r = 1.0 / Z;
+    double apr[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+        apr[i] = ap[i] * r;
+    double tot = apr[0];
+#pragma unroll
+    for (int i = 1; i < K; ++i)
+        tot += apr[i];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        double sj = 0.0;
+        bool first = true;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            if (KNOWN && (!on[j] || !tayal_nz(i < 4 ? i : 0, j < 4 ? j : 0)))
+                continue;
+            sj = first ? apr[i] * pp.A[i][j] : fma(apr[i], pp.A[i][j], sj);
+            first = false;
+        }
+        g[j] = (on[j] ? sj : tot) * b[j];
+    }
+    /* A is constant over the steps: xi accumulates alpha_{t-1}(i) b_t(j) / Z over
+     * the "on" steps and takes its factor A(i,j) once, at the end */
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if (KNOWN && !on[j])
+            continue;
+        const double bm = on[j] ? b[j] : 0.0;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            if (KNOWN && !tayal_nz(i < 4 ? i : 0, j < 4 ? j : 0))
+                continue;
+            xi[i][j] = fma(apr[i], bm, xi[i][j]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+        be[i] = bn[i];
+    int ex = 0;
+    renorm<K>(be, ex);
+    return Z;
+}
+
+/* gamma of one step into row x of the c_kl slab (clamped like the emission fetch) */
+template <int K>
+__device__ __forceinline__ void expect_emit_acc(double2 *cslab, int L, const Obs &o, const double (&g)[K])
+{
+    constexpr int KP = (K + 1) / 2;
+    const int xc = min(max(o.x, 1), L);
+    double2 *r = (cslab - KP * 64) + xc * (KP * 64);
+#pragma unroll
+    for (int kp = 0; kp < KP; ++kp) {
+        double2 v = r[kp * 64];
+        v.x += g[2 * kp];
+        if (2 * kp + 1 < K)
+            v.y += g[2 * kp + 1];
+        r[kp * 64] = v;
+    }
+}
+
+/* xcheck_acc for the auxiliary stream: the running max of aux - 1 (unsigned,
+ * so a value below 1 wraps above every bound) over the lane's own steps */
+template <int C, bool FULL>
+__device__ __forceinline__ void auxcheck_acc(uint32_t &am, const Obs (&o)[C], int c, int Tp)
+{
+#pragma unroll
+    for (int v = 0; v < C; ++v)
+        am = max(am, (FULL || c * C + v < Tp) ? ((uint32_t)o[v].aux - 1u) : 0u);
+}
+
+template <int MODEL, int K>
+__global__ void __launch_bounds__(kBlock) expect_kernel(const DevArgs a, const ExpectOut o)
+{
+    static_assert(ModelTraits<MODEL>::kAux, "the masked programs; hmm-multinom runs estep_kernel");
+    constexpr int C = fb_chunk(K);
+    constexpr int KP = (K + 1) / 2;
+    HIP_DYNAMIC_SHARED(double2, lds)
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int nw = blockDim.x >> 6;
+    const int64_t gwave = (int64_t)blockIdx.x * nw + wave;
+    /* lanes past the last pair redo pair P-1 (identical values, benign
+     * duplicate stores): every lane stays in the wave-wide reductions */
+    const int64_t p = min(gwave * 64 + lane, a.P - 1);
+    int64_t n, d;
+    pair_coords(a, p, n, d);
+
+    FbLane<MODEL, K> ln;
+    ln.p = p;
+    ln.n = n;
+    ln.L = a.L;
+    ln.t0 = 0;
+    ln.Tp = pair_len(a, n);
+    ln.cb = 0;
+    ln.q = p;
+    ln.Qs = a.P;
+    const size_t slab_elems = (size_t)a.L * KP * 64;
+    double2 *const pslab = lds + (size_t)wave * slab_elems + lane;
+    double2 *const cslab = lds + (size_t)(nw + wave) * slab_elems + lane;
+    ln.slab = pslab;
+    load_params<MODEL, K, false>(ln.pp, a, d);
+    ln.pp.skip_ok &= fill_table<K, false>(pslab, a, d);
+    for (int i = 0; i < a.L * KP; ++i)
+        cslab[i * 64] = make_double2(0.0, 0.0);
+    const SeriesPtrs sp = series_ptrs<MODEL, true>(a, n);
+    const int Tw_min = wave_min(ln.Tp);
+    const int Tw_max = wave_max(ln.Tp);
+    const int nfull = Tw_min / C;            /* chunks complete for every lane */
+    const int nchunk = (Tw_max + C - 1) / C; /* chunks any lane needs: <= ceil(Tmax / C) checkpoint rows */
+
+    /* ---- forward sweep: fb_kernel's (masked), checkpoints only ---- */
+    double ll;
+    uint32_t xm = 0, am = 0;
+    Obs cur[C];
+    {
+        double al[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            al[k] = 0.0;
+        double lsc = 0.0;
+        int ex = 0;
+        constexpr int D = kFwdGroup;
+        Obs grp[D][C];
+#pragma unroll
+        for (int i = 0; i < D; ++i)
+            load_chunk<MODEL, C, true>(grp[i], sp, i * C);
+        Em<K> ecur;
+        emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, grp[0][0], ecur);
+        int c = 0;
+        for (; c + D <= nfull; c += D) {
+            Obs nxt[D][C];
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+                load_chunk<MODEL, C, true>(nxt[i], sp, (c + D + i) * C);
+#pragma unroll
+            for (int i = 0; i < D; ++i) {
+                fwd_chunk<MODEL, K, C, FB_GAMMA, true>(a, ln, c + i, grp[i],
+                                                       (i + 1 < D) ? grp[i + 1 < D ? i + 1 : 0][0] : nxt[0][0], ecur,
+                                                       al, lsc, ex);
+                xcheck_acc<C, true>(xm, grp[i], c + i, ln.Tp);
+                auxcheck_acc<C, true>(am, grp[i], c + i, ln.Tp);
+            }
+#pragma unroll
+            for (int i = 0; i < D; ++i)
+#pragma unroll
+                for (int u = 0; u < C; ++u)
+                    grp[i][u] = nxt[i][u];
+        }
+#pragma unroll
+        for (int u = 0; u < C; ++u)
+            cur[u] = grp[0][u];
+        for (; c < nchunk; ++c) {
+            Obs nxt[C];
+            load_chunk<MODEL, C, true>(nxt, sp, (c + 1) * C);
+            fwd_chunk<MODEL, K, C, FB_GAMMA, false>(a, ln, c, cur, nxt[0], ecur, al, lsc, ex);
+            xcheck_acc<C, false>(xm, cur, c, ln.Tp);
+            auxcheck_acc<C, false>(am, cur, c, ln.Tp);
+#pragma unroll
+            for (int u = 0; u < C; ++u)
+                cur[u] = nxt[u];
+        }
+        ll = log(vsum<K>(al)) + (lsc + kLn2 * ex);
+    }
+
+    /* ---- backward sweep, chunk by chunk from the end ---- */
+    double xi[K][K], be[K], n1[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+        be[i] = 1.0; /* beta_T = 1 */
+        n1[i] = 0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            xi[i][j] = 0.0;
+    }
+    bool bad = !__builtin_isfinite(ll);
+    int aux1 = 0; /* g_1 / sign_1 */
+    const int clast = nchunk - 1;
+    load_chunk<MODEL, C, true>(cur, sp, clast * C);
+    /* checkpoint rows are wave-uniform: a lane shorter than the wave reads
+     * (unused) slots past its own last chunk, never past the allocation */
+    double ck[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        ck[k] = get_tmp(a.ckpt + a.P * ((int64_t)clast * K + k), (uint32_t)p * 8u);
+    Obs onext = cur[0];
+    for (int c = clast; c >= 0; --c) {
+        const int t0 = c * C;
+        Obs nxt[C];
+        load_chunk<MODEL, C, true>(nxt, sp, (c - 1) * C);
+        double cn[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            cn[k] = get_tmp(a.ckpt + a.P * ((int64_t)max(c - 1, 0) * K + k), (uint32_t)p * 8u);
+        /* alpha over the chunk from its checkpoint */
+        double abuf[C][K];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            abuf[0][k] = ck[k];
+        {
+            int exb = 0;
+            Em<K> ecur;
+            emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, cur[1 < C ? 1 : 0], ecur);
+#pragma unroll
+            for (int u = 1; u < C; ++u) {
+                Em<K> enx;
+                emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, cur[u + 1 < C ? u + 1 : u], enx);
+                if (t0 + u < ln.Tp) {
+                    /* Tayal: fwd_step_to without its sign-class dispatch (the same
+                     * bits): the recompute of a chunk stays straight-line code */
+                    if constexpr (ModelTraits<MODEL>::kTayal) {
+                        fwd_step_raw<MODEL, K>(abuf[u - 1], abuf[u], ln.pp, ecur.e, cur[u]);
+                        renorm<K>(abuf[u], exb);
+                    } else {
+                        fwd_step_to<MODEL, K>(abuf[u - 1], abuf[u], ln.pp, ecur.e, cur[u], exb);
+                    }
+                }
+                ecur = enx;
+            }
+        }
+        /* transitions into steps t0 + C (the next chunk's first) .. t0 + 1 */
+        Em<K> ecur;
+        emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, onext, ecur);
+#pragma unroll
+        for (int v = C; v >= 1; --v) {
+            const Obs &ob = (v < C) ? cur[v < C ? v : 0] : onext;
+            Em<K> enx;
+            emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, cur[v - 1 >= 1 ? v - 1 : 1], enx);
+            if (t0 + v < ln.Tp) {
+                double g[K];
+                double Z = 0.0;
+                tayal_dispatch<MODEL>(ob, ln.pp.skip_ok, [&](auto sgc) {
+                    Z = expect_transition<MODEL, K, decltype(sgc)::value>(ln.pp, abuf[v - 1], ecur.e, ob, be, xi, g);
+                });
+                bad |= !((Z > 0.0) & (Z < __builtin_inf()));
+                expect_emit_acc<K>(cslab, a.L, ob, g);
+            }
+            ecur = enx;
+        }
+        if (c == 0) { /* the first step: gamma_1 = alpha_1 .* beta_1 / their sum */
+            double Z = 0.0;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                n1[k] = abuf[0][k] * be[k];
+                Z += n1[k];
+            }
+            const double r = 1.0 / Z;
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+                n1[k] *= r;
+            bad |= !((Z > 0.0) & (Z < __builtin_inf()));
+            expect_emit_acc<K>(cslab, a.L, cur[0], n1);
+            aux1 = cur[0].aux;
+        }
+        onext = cur[0];
+#pragma unroll
+        for (int u = 0; u < C; ++u)
+            cur[u] = nxt[u];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            ck[k] = cn[k];
+    }
+
+    /* ---- the [P, ...] outputs ---- */
+    const uint32_t po = (uint32_t)p * 8u;
+    const double nanv = dev_nan();
+    put_out(o.loglik, po, ll);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        bool p1 = true; /* Tayal: the init factor p_1k applies at (sign_1, k) */
+        if constexpr (ModelTraits<MODEL>::kTayal)
+            p1 = tayal_init_pred(aux1, k);
+        put_out(o.n1 + a.P * (int64_t)k, po, bad ? nanv : p1 ? n1[k] : 0.0);
+    }
+    /* an entry no step switched on is 0 whatever A(i,j) is */
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+#pragma unroll
+        for (int i = 0; i < K; ++i)
+            put_out(o.xi + a.P * (int64_t)(i + K * j), po,
+                    bad ? nanv : xi[i][j] != 0.0 ? ln.pp.A[i][j] * xi[i][j] : 0.0);
+    for (int l = 0; l < a.L; ++l) {
+#pragma unroll
+        for (int kp = 0; kp < KP; ++kp) {
+            const double2 v = cslab[(l * KP + kp) * 64];
+            put_out(o.c + a.P * ((int64_t)(2 * kp) + (int64_t)K * l), po, bad ? nanv : v.x);
+            if (2 * kp + 1 < K)
+                put_out(o.c + a.P * ((int64_t)(2 * kp + 1) + (int64_t)K * l), po, bad ? nanv : v.y);
+        }
+    }
+    if (o.status) {
+        bool inv = xm >= (uint32_t)a.L || am >= (uint32_t)o.ahi;
+        if (a.T)
+            inv |= a.T[n] < 1 || a.T[n] > a.Tmax;
+        o.status[p] = inv ? HHMM_PAIR_INVALID_DATA : HHMM_PAIR_OK;
+    }
+}
+
+/* Waves per workgroup and its LDS: the E-step's two slabs per wave. */
+static int expect_waves(int K, int L, size_t *lds)
+{
+    const size_t per_wave = 2 * (size_t)L * (size_t)((K + 1) / 2) * 64 * sizeof(double2);
+    int waves = kBlock / 64;
+    while (waves > 0 && per_wave * waves > kLdsLimit)
+        --waves;
+    *lds = per_wave * waves;
+    return waves;
+}
+
+static bool expect_model(int m)
+{
+    return m == HHMM_MODEL_HMM_MULTINOM || m == HHMM_MODEL_HMM_MULTINOM_SEMISUP || m == HHMM_MODEL_TAYAL;
+}
+
+hhmm_status check_expected_stats(const hhmm_request *r, const hhmm_estep_result *o)
+{
+    if (!r) {
+        set_error("request must be non-NULL");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (r->abi_version != HHMM_ABI_VERSION) {
+        set_error("abi_version %u != %u", r->abi_version, HHMM_ABI_VERSION);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (r->model < 1 || r->model > 9) {
+        set_error("unknown model id %d", r->model);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (!expect_model(r->model)) {
+        set_error("expected statistics: model %d is not supported (hmm-multinom, hmm-multinom-semisup and "
+                  "hhmm-tayal2009 only; the Gaussian hmm has hhmm_estep)",
+                  r->model);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if (r->data.K > kMaxK) {
+        set_error("expected statistics: K = %d, the lane-per-pair kernel supports K <= %d", r->data.K, kMaxK);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if (r->device == HHMM_DEVICE_SET) {
+        set_error("expected statistics: HHMM_DEVICE_SET is not supported (one device per call)");
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if (r->data.K >= 1 && r->data.L >= 1) {
+        size_t lds;
+        if (expect_waves(r->data.K, r->data.L, &lds) < 1) {
+            set_error("expected statistics: L * ceil(K / 2) = %d * %d > 80: the emission table and its count table "
+                      "of one wave do not fit in LDS",
+                      r->data.L, (r->data.K + 1) / 2);
+            return HHMM_ERR_UNSUPPORTED;
+        }
+    }
+    if (!o) {
+        set_error("expected statistics result must be non-NULL");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (!o->loglik || !o->n_1k || !o->xi_ij || !o->c_kl) {
+        set_error("expected statistics: loglik, n_1k, xi_ij and c_kl must be non-NULL");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    return HHMM_OK;
+}
+
+template <int MODEL, int K>
+static void launch_expect_k(const DevArgs &a, const ExpectOut &o, dim3 grid, dim3 block, size_t lds, hipStream_t st)
+{
+    hipLaunchKernelGGL((expect_kernel<MODEL, K>), grid, block, lds, st, a, o);
+}
+
+template <int MODEL>
+static bool launch_expect_m(const DevArgs &a, const ExpectOut &o, dim3 grid, dim3 block, size_t lds, hipStream_t st)
+{
+    switch (a.K) {
+    case 1: launch_expect_k<MODEL, 1>(a, o, grid, block, lds, st); return true;
+    case 2: launch_expect_k<MODEL, 2>(a, o, grid, block, lds, st); return true;
+    case 3: launch_expect_k<MODEL, 3>(a, o, grid, block, lds, st); return true;
+    case 4: launch_expect_k<MODEL, 4>(a, o, grid, block, lds, st); return true;
+    case 5: launch_expect_k<MODEL, 5>(a, o, grid, block, lds, st); return true;
+    case 6: launch_expect_k<MODEL, 6>(a, o, grid, block, lds, st); return true;
+    case 7: launch_expect_k<MODEL, 7>(a, o, grid, block, lds, st); return true;
+    case 8: launch_expect_k<MODEL, 8>(a, o, grid, block, lds, st); return true;
+    default: return false;
+    }
+}
+
+hhmm_status launch_expected_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
+                                  hipStream_t st)
+{
+    if (r->model == HHMM_MODEL_HMM_MULTINOM) /* no mask: the E-step itself */
+        return launch_estep(r, res, P, ws, st);
+    DevArgs a{};
+    a.P = P;
+    a.N = r->data.n_series;
+    a.S = r->draws.n_draws;
+    a.pairing = r->pairing;
+    a.model = r->model;
+    a.K = r->data.K;
+    a.L = r->data.L;
+    a.Tmax = r->data.T_max;
+    a.Tout = r->data.T_max;
+    a.T = r->data.T;
+    a.x = r->data.x_int;
+    a.g = r->data.g;
+    a.sign = r->data.sign;
+    a.p_1k = r->draws.p_1k;
+    a.A_ij = r->draws.A_ij;
+    a.phi_k = r->draws.phi_k;
+    a.p_11 = r->draws.p_11;
+    a.A_row = r->draws.A_row;
+    a.ckpt = (double *)ws;
+    ExpectOut o{res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->pair_status,
+                r->model == HHMM_MODEL_TAYAL ? 2 : r->data.G};
+    size_t lds = 0;
+    const int waves = expect_waves(a.K, a.L, &lds);
+    if (waves < 1) {
+        set_error("expected statistics: the tables of K*L = %d*%d do not fit in LDS", a.K, a.L);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    const int threads = 64 * waves;
+    const dim3 grid((unsigned)((P + threads - 1) / threads)), block(threads);
+    bool ok = false;
+    if (a.model == HHMM_MODEL_HMM_MULTINOM_SEMISUP)
+        ok = launch_expect_m<HHMM_MODEL_HMM_MULTINOM_SEMISUP>(a, o, grid, block, lds, st);
+    else if (a.model == HHMM_MODEL_TAYAL && a.K == 4) {
+        launch_expect_k<HHMM_MODEL_TAYAL, 4>(a, o, grid, block, lds, st);
+        ok = true;
+    }
+    if (!ok) {
+        set_error("expected statistics: model %d at K = %d has no kernel (K outside 1..%d)", a.model, a.K, kMaxK);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error("expect_kernel launch: %s", hipGetErrorString(e));
+        return HHMM_ERR_HIP;
+    }
+    return HHMM_OK;
+}
+
+} // namespace hhmm

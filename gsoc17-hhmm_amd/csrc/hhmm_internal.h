@@ -13,6 +13,7 @@
 #include "hhmm_summary.h"
 #include "hhmm_estep.h"
 #include "hhmm_gibbs.h"
+#include "hhmm_expect.h"
 
 namespace hhmm {
 
@@ -228,6 +229,13 @@ hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, in
 hhmm_status check_draw_stats(const hhmm_request *r, const hhmm_estep_result *o);
 hhmm_status launch_draw_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                               hipStream_t st);
+
+/* Expected draw statistics (hhmm_expect.hip): argument checks (no device
+ * needed) and the launch on `st` (device pointers); the workspace is the
+ * E-step's, and hmm-multinom goes to launch_estep. */
+hhmm_status check_expected_stats(const hhmm_request *r, const hhmm_estep_result *o);
+hhmm_status launch_expected_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
+                                  hipStream_t st);
 
 /* Tick -> zig-zag -> leg feature extractor (hhmm_features.hip). */
 size_t features_workspace_bytes(int64_t n);

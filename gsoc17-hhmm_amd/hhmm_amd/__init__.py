@@ -12,6 +12,7 @@ from . import _abi  # noqa: F401
 from .api import HHMMError, PreparedRequest, gqs, load_library, reshape_pairs  # noqa: F401
 from .summary import gqs_summary, quantiles  # noqa: F401
 from .estep import estep, m_step, score  # noqa: F401
+from .expect import expected_stats  # noqa: F401
 from .em import baum_welch  # noqa: F401
 from .gibbs import conditional_draw, draw_stats, gibbs, stack_chains  # noqa: F401
 

@@ -334,4 +334,11 @@ def declare(lib):
     lib.hhmm_draw_stats_device.restype = C.c_int
     lib.hhmm_draw_stats.argtypes = [RP, EP]
     lib.hhmm_draw_stats.restype = C.c_int
+    # include/hhmm_expect.h (the result struct is the E-step's)
+    lib.hhmm_expected_stats_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
+    lib.hhmm_expected_stats_workspace_size.restype = C.c_int
+    lib.hhmm_expected_stats_device.argtypes = [RP, EP, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.hhmm_expected_stats_device.restype = C.c_int
+    lib.hhmm_expected_stats.argtypes = [RP, EP]
+    lib.hhmm_expected_stats.restype = C.c_int
     return lib

@@ -14,6 +14,11 @@ The statistics follow the CODED likelihood of each Stan program: hmm.stan:30
 adds sum_k normal_lpdf(x_1 | mu_k, sigma_k) to every state at t = 1 (quirk Q2),
 so x_1 enters w_k / s1_k / s2_k with weight 1 for every state.  hmm and
 hmm-multinom at K <= 8.
+
+score() and m_step() also take the statistics hhmm_amd.expected_stats returns
+for the two masked programs (FIT_MODELS): hmm-multinom-semisup with the
+hmm-multinom formulas, hhmm-tayal2009 in the parameters the program has --
+p_11, the two rows of A_row and phi_k.
 """
 import ctypes as C
 
@@ -23,6 +28,7 @@ from . import _abi
 from .api import HHMMError, PreparedRequest, load_library
 
 MODELS = ("hmm", "hmm-multinom")
+FIT_MODELS = MODELS + ("hmm-multinom-semisup", "hhmm-tayal2009")  # score / m_step / baum_welch
 _TINY = 1e-300
 
 
@@ -97,17 +103,25 @@ def _ratio(count, par):
 def score(model, draws, stats, pairing, S, N):
     """Gradient of loglik with respect to the constrained parameters, per pair.
 
-    {name: (P, ...)} for p_1k, A_ij and phi_k (hmm-multinom) or mu_k, sigma_k
-    (hmm), by Fisher's identity from the statistics of estep().  The simplex
-    parameters are treated as free coordinates: a directional derivative along
-    a tangent of the simplex is the matching difference of entries."""
-    if model not in MODELS:
-        raise ValueError(f"the E-step covers {MODELS}, not {model!r}")
+    {name: (P, ...)} for p_1k, A_ij and phi_k (hmm-multinom, semisup) or mu_k,
+    sigma_k (hmm), by Fisher's identity from the statistics of estep() or
+    expected_stats().  hhmm-tayal2009: p_11 (P,), n1[0] / p_11 - n1[2] / (1 -
+    p_11); A_row (P, 2, 2), (xi[0,1], xi[0,2]) / A_row[0] and (xi[2,0], xi[2,3])
+    / A_row[1]; phi_k.  The simplex parameters are treated as free coordinates:
+    a directional derivative along a tangent of the simplex is the matching
+    difference of entries."""
+    if model not in FIT_MODELS:
+        raise ValueError(f"score covers {FIT_MODELS}, not {model!r}")
     P = stats["loglik"].shape[0]
     d = pair_draw(pairing, P, S, N)
+    if model == "hhmm-tayal2009":
+        n1, p11 = stats["n_1k"], np.asarray(draws["p_11"], dtype=np.float64)[d]
+        return {"p_11": _ratio(n1[:, 0], p11) - _ratio(n1[:, 2], 1.0 - p11),
+                "A_row": _ratio(tayal_rows(stats["xi_ij"]), np.asarray(draws["A_row"])[d]),
+                "phi_k": _ratio(stats["c_kl"], np.asarray(draws["phi_k"])[d])}
     g = {"p_1k": _ratio(stats["n_1k"], np.asarray(draws["p_1k"])[d]),
          "A_ij": _ratio(stats["xi_ij"], np.asarray(draws["A_ij"])[d])}
-    if model == "hmm-multinom":
+    if model != "hmm":
         g["phi_k"] = _ratio(stats["c_kl"], np.asarray(draws["phi_k"])[d])
     else:
         mu, sg = np.asarray(draws["mu_k"])[d], np.asarray(draws["sigma_k"])[d]
@@ -115,6 +129,12 @@ def score(model, draws, stats, pairing, S, N):
         g["mu_k"] = (s1 - mu * w) / sg ** 2
         g["sigma_k"] = -w / sg + (s2 - 2 * mu * s1 + mu ** 2 * w) / sg ** 3
     return g
+
+
+def tayal_rows(xi):
+    """(P, 2, 2): the counts of A_row's entries inside xi_ij (hhmm-tayal2009.stan:36-44)."""
+    return np.stack([np.stack([xi[:, 0, 1], xi[:, 0, 2]], axis=-1),
+                     np.stack([xi[:, 2, 0], xi[:, 2, 3]], axis=-1)], axis=1)
 
 
 def _rows(counts, prev):
@@ -130,13 +150,23 @@ def m_step(model, stats, prev=None):
 
     p_1k = n_1k; rows of A and phi are counts over their row sums (a row whose
     sum is 0 keeps its value in `prev`, {name: (P, ...)}); mu = s1 / w;
-    sigma = sqrt(max(s2 / w - mu^2, tiny))."""
-    if model not in MODELS:
-        raise ValueError(f"the E-step covers {MODELS}, not {model!r}")
+    sigma = sqrt(max(s2 / w - mu^2, tiny)).  hhmm-tayal2009 (tied parameters):
+    p_11 = n1[0] / (n1[0] + n1[2]), the rows of A_row are (xi[0,1], xi[0,2]) and
+    (xi[2,0], xi[2,3]) over their sums, phi_k as above; a zero total keeps
+    `prev`."""
+    if model not in FIT_MODELS:
+        raise ValueError(f"m_step covers {FIT_MODELS}, not {model!r}")
     xi = stats["xi_ij"]
+    if model == "hhmm-tayal2009":
+        n1, c, rows = stats["n_1k"], stats["c_kl"], tayal_rows(xi)
+        tot = n1[:, 0] + n1[:, 2]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            p11 = np.where(tot == 0, prev["p_11"] if prev is not None else np.nan, n1[:, 0] / tot)
+        return {"p_11": p11, "A_row": _rows(rows, prev["A_row"] if prev is not None else np.full(rows.shape, np.nan)),
+                "phi_k": _rows(c, prev["phi_k"] if prev is not None else np.full(c.shape, np.nan))}
     pa = prev["A_ij"] if prev is not None else np.full(xi.shape, np.nan)
     new = {"p_1k": np.array(stats["n_1k"]), "A_ij": _rows(xi, pa)}
-    if model == "hmm-multinom":
+    if model != "hmm":
         c = stats["c_kl"]
         new["phi_k"] = _rows(c, prev["phi_k"] if prev is not None else np.full(c.shape, np.nan))
     else:
