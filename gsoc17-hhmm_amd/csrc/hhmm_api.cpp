@@ -2536,6 +2536,149 @@ hhmm_status hhmm_draw_stats(const hhmm_request *req, hhmm_estep_result *res)
 } // extern "C"
 
 /* ------------------------------------------------------------------ */
+/* Gaussian draw statistics entry points (include/hhmm_gibbs_gauss.h)   */
+/* ------------------------------------------------------------------ */
+
+/* Argument checks of both entries, none of which needs a device: the entry's
+ * own scope and the uniforms first, then the request as hhmm_run /
+ * hhmm_run_device check it for hmm (host: the data-block bounds too). */
+static hhmm_status draw_stats_gauss_check(const hhmm_request *req, const hhmm_estep_result *res, bool host)
+{
+    hhmm_status s = check_draw_stats_gauss(req, res);
+    if (s != HHMM_OK)
+        return s;
+    hhmm_request r2 = *req; /* outputs and hat_rand are ignored */
+    r2.outputs = HHMM_OUT_LOGLIK;
+    r2.hat_rand = nullptr;
+    return validate_impl(&r2, nullptr, host);
+}
+
+extern "C" {
+
+hhmm_status hhmm_draw_stats_gauss_workspace_size(const hhmm_request *req, size_t *bytes)
+{
+    if (!req || !bytes) {
+        set_error("NULL argument");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    const int64_t P = npairs(req);
+    if (P < 1 || req->data.K < 1 || req->data.T_max < 1) {
+        set_error("request describes no pairs");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (req->data.K > kMaxK) {
+        set_error("Gaussian draw statistics: K = %d, the lane-per-pair kernel supports K <= %d", req->data.K, kMaxK);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    *bytes = estep_workspace_bytes(req->data.K, req->data.T_max, P);
+    return HHMM_OK;
+}
+
+hhmm_status hhmm_draw_stats_gauss_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                                         size_t workspace_bytes_, void *stream)
+{
+    hhmm_status s = draw_stats_gauss_check(req, res, false);
+    if (s != HHMM_OK)
+        return s;
+    if ((s = check_device()) != HHMM_OK)
+        return s;
+    const int64_t P = npairs(req);
+    const size_t need = estep_workspace_bytes(req->data.K, req->data.T_max, P);
+    if (workspace_bytes_ < need || !workspace) {
+        set_error("workspace of %zu bytes < %zu required", workspace_bytes_, need);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    return launch_draw_stats_gauss(req, res, P, workspace, (hipStream_t)stream);
+}
+
+hhmm_status hhmm_draw_stats_gauss(const hhmm_request *req, hhmm_estep_result *res)
+{
+    hhmm_status s = draw_stats_gauss_check(req, res, true);
+    if (s != HHMM_OK)
+        return s;
+    if ((s = check_device()) != HHMM_OK)
+        return s;
+    int dev = req->device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess)
+        return hip_fail(hipGetLastError(), "hipGetDevice");
+    hipError_t e = hipSetDevice(dev);
+    if (e != hipSuccess)
+        return hip_fail(e, "hipSetDevice");
+    const hhmm_data &d = req->data;
+    const hhmm_draws &w = req->draws;
+    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max, K = (size_t)d.K;
+    const size_t P = (size_t)npairs(req);
+    hhmm_request dr = *req;
+    hhmm_estep_result dq{};
+    struct Arr {
+        const void *host_in;
+        void *host_out;
+        void **dev;
+        size_t bytes;
+    } arrs[] = {
+        {d.T, nullptr, (void **)&dr.data.T, d.T ? N * 4 : 0},
+        {d.x_real, nullptr, (void **)&dr.data.x_real, N * Tm * 8},
+        {w.p_1k, nullptr, (void **)&dr.draws.p_1k, S * K * 8},
+        {w.A_ij, nullptr, (void **)&dr.draws.A_ij, S * K * K * 8},
+        {w.mu_k, nullptr, (void **)&dr.draws.mu_k, S * K * 8},
+        {w.sigma_k, nullptr, (void **)&dr.draws.sigma_k, S * K * 8},
+        {req->ffbs_u, nullptr, (void **)&dr.ffbs_u, P * Tm * 8},
+        {nullptr, res->loglik, (void **)&dq.loglik, P * 8},
+        {nullptr, res->n_1k, (void **)&dq.n_1k, P * K * 8},
+        {nullptr, res->xi_ij, (void **)&dq.xi_ij, P * K * K * 8},
+        {nullptr, res->w_k, (void **)&dq.w_k, P * K * 8},
+        {nullptr, res->s1_k, (void **)&dq.s1_k, P * K * 8},
+        {nullptr, res->s2_k, (void **)&dq.s2_k, P * K * 8},
+        {nullptr, res->pair_status, (void **)&dq.pair_status, res->pair_status ? P * 4 : 0},
+    };
+    /* one pooled block: every array at a 256-byte boundary, then the workspace */
+    size_t total = 0;
+    std::vector<size_t> off;
+    for (const Arr &a : arrs) {
+        off.push_back(total);
+        if ((a.host_in || a.host_out) && a.bytes)
+            total += (a.bytes + 255) & ~(size_t)255;
+    }
+    const size_t wsb = estep_workspace_bytes(d.K, d.T_max, (int64_t)P);
+    char *blk = (char *)pool_get(dev, total);
+    void *ws = pool_get(dev, wsb);
+    auto cleanup = [&]() {
+        pool_put(blk);
+        pool_put(ws);
+    };
+    if (!blk || !ws) {
+        cleanup();
+        set_error("device %d: Gaussian draw statistics allocation of %zu + %zu bytes failed", dev, total, wsb);
+        return HHMM_ERR_OUT_OF_MEMORY;
+    }
+    for (size_t i = 0; i < sizeof(arrs) / sizeof(arrs[0]) && e == hipSuccess; ++i) {
+        const Arr &a = arrs[i];
+        const bool used = (a.host_in || a.host_out) && a.bytes;
+        *a.dev = used ? (void *)(blk + off[i]) : nullptr;
+        if (used && a.host_in)
+            e = hipMemcpy(*a.dev, a.host_in, a.bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        cleanup();
+        return hip_fail(e, "Gaussian draw statistics upload");
+    }
+    s = launch_draw_stats_gauss(&dr, &dq, (int64_t)P, ws, nullptr);
+    e = hipStreamSynchronize(nullptr); /* before the pooled blocks can go to another request */
+    if (s == HHMM_OK && e == hipSuccess)
+        for (const Arr &a : arrs)
+            if (a.host_out && a.bytes && e == hipSuccess)
+                e = hipMemcpy(a.host_out, *a.dev, a.bytes, hipMemcpyDeviceToHost);
+    cleanup();
+    if (s != HHMM_OK)
+        return s;
+    if (e != hipSuccess)
+        return hip_fail(e, "Gaussian draw statistics (kernel execution or download)");
+    return HHMM_OK;
+}
+
+} // extern "C"
+
+/* ------------------------------------------------------------------ */
 /* Expected draw statistics entry points (include/hhmm_expect.h)        */
 /* ------------------------------------------------------------------ */
 

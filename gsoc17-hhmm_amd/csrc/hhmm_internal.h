@@ -13,6 +13,7 @@
 #include "hhmm_summary.h"
 #include "hhmm_estep.h"
 #include "hhmm_gibbs.h"
+#include "hhmm_gibbs_gauss.h"
 #include "hhmm_expect.h"
 
 namespace hhmm {
@@ -229,6 +230,12 @@ hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, in
 hhmm_status check_draw_stats(const hhmm_request *r, const hhmm_estep_result *o);
 hhmm_status launch_draw_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                               hipStream_t st);
+
+/* Gaussian draw statistics (hhmm_draw_stats_gauss.hip): the same pair for
+ * hmm.stan; the workspace is the E-step's. */
+hhmm_status check_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_result *o);
+hhmm_status launch_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
+                                    hipStream_t st);
 
 /* Expected draw statistics (hhmm_expect.hip): argument checks (no device
  * needed) and the launch on `st` (device pointers); the workspace is the

@@ -334,6 +334,13 @@ def declare(lib):
     lib.hhmm_draw_stats_device.restype = C.c_int
     lib.hhmm_draw_stats.argtypes = [RP, EP]
     lib.hhmm_draw_stats.restype = C.c_int
+    # include/hhmm_gibbs_gauss.h (the result struct is the E-step's)
+    lib.hhmm_draw_stats_gauss_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
+    lib.hhmm_draw_stats_gauss_workspace_size.restype = C.c_int
+    lib.hhmm_draw_stats_gauss_device.argtypes = [RP, EP, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.hhmm_draw_stats_gauss_device.restype = C.c_int
+    lib.hhmm_draw_stats_gauss.argtypes = [RP, EP]
+    lib.hhmm_draw_stats_gauss.restype = C.c_int
     # include/hhmm_expect.h (the result struct is the E-step's)
     lib.hhmm_expected_stats_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
     lib.hhmm_expected_stats_workspace_size.restype = C.c_int
