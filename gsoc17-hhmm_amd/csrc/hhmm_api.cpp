@@ -2241,586 +2241,228 @@ hhmm_status hhmm_extract_features(const hhmm_ticks *ticks, hhmm_legs *legs, int 
 } // extern "C"
 
 /* ------------------------------------------------------------------ */
-/* Batched E-step entry points (include/hhmm_estep.h)                   */
+/* Statistics per (series, draw) pair: the E-step (include/hhmm_estep.h), */
+/* the draw statistics (hhmm_gibbs.h, hhmm_gibbs_gauss.h) and the expected */
+/* draw statistics (hhmm_expect.h) share one host path                  */
 /* ------------------------------------------------------------------ */
 
-/* Argument checks of both entries, none of which needs a device: the E-step's
- * own scope first (HHMM_ERR_UNSUPPORTED names the reason), then the request as
- * hhmm_run / hhmm_run_device check it (host: the data-block bounds too). */
-static hhmm_status estep_check(const hhmm_request *req, const hhmm_estep_result *res, bool host)
+/* What tells the four entries apart on the host. */
+struct StatsEntry {
+    const char *name; /* in messages */
+    bool reads_u;     /* ffbs_u is an input (elsewhere the field is ignored) */
+    hhmm_status (*check)(const hhmm_request *, const hhmm_estep_result *);
+    hhmm_status (*launch)(const hhmm_request *, const hhmm_estep_result *, int64_t, void *, hipStream_t);
+};
+static const StatsEntry kEstep = {"E-step", false, check_estep, launch_estep};
+static const StatsEntry kDrawStats = {"draw statistics", true, check_draw_stats, launch_draw_stats};
+static const StatsEntry kDrawStatsGauss = {"Gaussian draw statistics", true, check_draw_stats_gauss,
+                                           launch_draw_stats_gauss};
+static const StatsEntry kExpectedStats = {"expected statistics", false, check_expected_stats, launch_expected_stats};
+
+/* Argument checks of the device and the host entry, none of which needs a
+ * device: the entry's own scope first (HHMM_ERR_UNSUPPORTED names the reason),
+ * then the request as hhmm_run / hhmm_run_device check it (host: the
+ * data-block bounds too). */
+static hhmm_status stats_check(const StatsEntry &en, const hhmm_request *req, const hhmm_estep_result *res, bool host)
 {
-    hhmm_status s = check_estep(req, res);
+    hhmm_status s = en.check(req, res);
     if (s != HHMM_OK)
         return s;
-    hhmm_request r2 = *req; /* outputs, ffbs_u and hat_rand are ignored */
+    hhmm_request r2 = *req; /* outputs and hat_rand are ignored, ffbs_u unless the entry reads it */
     r2.outputs = HHMM_OUT_LOGLIK;
-    r2.ffbs_u = nullptr;
     r2.hat_rand = nullptr;
+    if (!en.reads_u)
+        r2.ffbs_u = nullptr;
     return validate_impl(&r2, nullptr, host);
+}
+
+static hhmm_status stats_workspace_size(const StatsEntry &en, const hhmm_request *req, size_t *bytes)
+{
+    if (!req || !bytes) {
+        set_error("NULL argument");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    const int64_t P = npairs(req);
+    if (P < 1 || req->data.K < 1 || req->data.T_max < 1) {
+        set_error("request describes no pairs");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (req->data.K > kMaxK) {
+        set_error("%s: K = %d, the lane-per-pair kernel supports K <= %d", en.name, req->data.K, kMaxK);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    *bytes = estep_workspace_bytes(req->data.K, req->data.T_max, P);
+    return HHMM_OK;
+}
+
+static hhmm_status stats_device(const StatsEntry &en, const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                                size_t workspace_bytes_, void *stream)
+{
+    hhmm_status s = stats_check(en, req, res, false);
+    if (s != HHMM_OK)
+        return s;
+    if ((s = check_device()) != HHMM_OK)
+        return s;
+    const int64_t P = npairs(req);
+    const size_t need = estep_workspace_bytes(req->data.K, req->data.T_max, P);
+    if (workspace_bytes_ < need || !workspace) {
+        set_error("workspace of %zu bytes < %zu required", workspace_bytes_, need);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    return en.launch(req, res, P, workspace, (hipStream_t)stream);
+}
+
+static hhmm_status stats_host(const StatsEntry &en, const hhmm_request *req, hhmm_estep_result *res)
+{
+    hhmm_status s = stats_check(en, req, res, true);
+    if (s != HHMM_OK)
+        return s;
+    if ((s = check_device()) != HHMM_OK)
+        return s;
+    int dev = req->device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess)
+        return hip_fail(hipGetLastError(), "hipGetDevice");
+    hipError_t e = hipSetDevice(dev);
+    if (e != hipSuccess)
+        return hip_fail(e, "hipSetDevice");
+    const hhmm_data &d = req->data;
+    const hhmm_draws &w = req->draws;
+    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max, K = (size_t)d.K;
+    const size_t P = (size_t)npairs(req);
+    const bool gauss = req->model == HHMM_MODEL_HMM_GAUSS; /* else one of the discrete programs */
+    const bool tayal = req->model == HHMM_MODEL_TAYAL;
+    const bool semisup = req->model == HHMM_MODEL_HMM_MULTINOM_SEMISUP;
+    const size_t L = gauss ? 0 : (size_t)d.L;
+    hhmm_request dr = *req;
+    hhmm_estep_result dq{};
+    /* a row is live when its host pointer is non-NULL and it has bytes; the
+     * device pointer of every other row is NULL */
+    struct Arr {
+        const void *host_in;
+        void *host_out;
+        void **dev;
+        size_t bytes;
+    } arrs[] = {
+        {d.T, nullptr, (void **)&dr.data.T, N * 4},
+        {gauss ? nullptr : d.x_int, nullptr, (void **)&dr.data.x_int, N * Tm * 4},
+        {gauss ? d.x_real : nullptr, nullptr, (void **)&dr.data.x_real, N * Tm * 8},
+        {semisup ? d.g : nullptr, nullptr, (void **)&dr.data.g, N * Tm * 4},
+        {tayal ? d.sign : nullptr, nullptr, (void **)&dr.data.sign, N * Tm * 4},
+        {tayal ? nullptr : w.p_1k, nullptr, (void **)&dr.draws.p_1k, S * K * 8},
+        {tayal ? nullptr : w.A_ij, nullptr, (void **)&dr.draws.A_ij, S * K * K * 8},
+        {tayal ? w.p_11 : nullptr, nullptr, (void **)&dr.draws.p_11, S * 8},
+        {tayal ? w.A_row : nullptr, nullptr, (void **)&dr.draws.A_row, S * 4 * 8},
+        {gauss ? nullptr : w.phi_k, nullptr, (void **)&dr.draws.phi_k, S * K * L * 8},
+        {gauss ? w.mu_k : nullptr, nullptr, (void **)&dr.draws.mu_k, S * K * 8},
+        {gauss ? w.sigma_k : nullptr, nullptr, (void **)&dr.draws.sigma_k, S * K * 8},
+        {en.reads_u ? req->ffbs_u : nullptr, nullptr, (void **)&dr.ffbs_u, P * Tm * 8},
+        {nullptr, res->loglik, (void **)&dq.loglik, P * 8},
+        {nullptr, res->n_1k, (void **)&dq.n_1k, P * K * 8},
+        {nullptr, res->xi_ij, (void **)&dq.xi_ij, P * K * K * 8},
+        {nullptr, gauss ? nullptr : res->c_kl, (void **)&dq.c_kl, P * K * L * 8},
+        {nullptr, gauss ? res->w_k : nullptr, (void **)&dq.w_k, P * K * 8},
+        {nullptr, gauss ? res->s1_k : nullptr, (void **)&dq.s1_k, P * K * 8},
+        {nullptr, gauss ? res->s2_k : nullptr, (void **)&dq.s2_k, P * K * 8},
+        {nullptr, res->pair_status, (void **)&dq.pair_status, P * 4},
+    };
+    /* one pooled block: every array at a 256-byte boundary, then the workspace */
+    size_t total = 0;
+    std::vector<size_t> off;
+    for (const Arr &a : arrs) {
+        off.push_back(total);
+        if ((a.host_in || a.host_out) && a.bytes)
+            total += (a.bytes + 255) & ~(size_t)255;
+    }
+    const size_t wsb = estep_workspace_bytes(d.K, d.T_max, (int64_t)P);
+    char *blk = (char *)pool_get(dev, total);
+    void *ws = pool_get(dev, wsb);
+    auto cleanup = [&]() {
+        pool_put(blk);
+        pool_put(ws);
+    };
+    if (!blk || !ws) {
+        cleanup();
+        set_error("device %d: %s allocation of %zu + %zu bytes failed", dev, en.name, total, wsb);
+        return HHMM_ERR_OUT_OF_MEMORY;
+    }
+    for (size_t i = 0; i < sizeof(arrs) / sizeof(arrs[0]) && e == hipSuccess; ++i) {
+        const Arr &a = arrs[i];
+        const bool used = (a.host_in || a.host_out) && a.bytes;
+        *a.dev = used ? (void *)(blk + off[i]) : nullptr;
+        if (used && a.host_in)
+            e = hipMemcpy(*a.dev, a.host_in, a.bytes, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) {
+        cleanup();
+        return hip_fail(e, (std::string(en.name) + " upload").c_str());
+    }
+    s = en.launch(&dr, &dq, (int64_t)P, ws, nullptr);
+    e = hipStreamSynchronize(nullptr); /* before the pooled blocks can go to another request */
+    if (s == HHMM_OK && e == hipSuccess)
+        for (const Arr &a : arrs)
+            if (a.host_out && a.bytes && e == hipSuccess)
+                e = hipMemcpy(a.host_out, *a.dev, a.bytes, hipMemcpyDeviceToHost);
+    cleanup();
+    if (s != HHMM_OK)
+        return s;
+    if (e != hipSuccess)
+        return hip_fail(e, (std::string(en.name) + " (kernel execution or download)").c_str());
+    return HHMM_OK;
 }
 
 extern "C" {
 
 hhmm_status hhmm_estep_workspace_size(const hhmm_request *req, size_t *bytes)
 {
-    if (!req || !bytes) {
-        set_error("NULL argument");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    const int64_t P = npairs(req);
-    if (P < 1 || req->data.K < 1 || req->data.T_max < 1) {
-        set_error("request describes no pairs");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (req->data.K > kMaxK) {
-        set_error("E-step: K = %d, the lane-per-pair kernel supports K <= %d", req->data.K, kMaxK);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    *bytes = estep_workspace_bytes(req->data.K, req->data.T_max, P);
-    return HHMM_OK;
+    return stats_workspace_size(kEstep, req, bytes);
 }
-
-hhmm_status hhmm_estep_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
-                              size_t workspace_bytes_, void *stream)
+hhmm_status hhmm_estep_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace, size_t workspace_bytes_,
+                              void *stream)
 {
-    hhmm_status s = estep_check(req, res, false);
-    if (s != HHMM_OK)
-        return s;
-    if ((s = check_device()) != HHMM_OK)
-        return s;
-    const int64_t P = npairs(req);
-    const size_t need = estep_workspace_bytes(req->data.K, req->data.T_max, P);
-    if (workspace_bytes_ < need || !workspace) {
-        set_error("workspace of %zu bytes < %zu required", workspace_bytes_, need);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    return launch_estep(req, res, P, workspace, (hipStream_t)stream);
+    return stats_device(kEstep, req, res, workspace, workspace_bytes_, stream);
 }
-
-hhmm_status hhmm_estep(const hhmm_request *req, hhmm_estep_result *res)
-{
-    hhmm_status s = estep_check(req, res, true);
-    if (s != HHMM_OK)
-        return s;
-    if ((s = check_device()) != HHMM_OK)
-        return s;
-    int dev = req->device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess)
-        return hip_fail(hipGetLastError(), "hipGetDevice");
-    hipError_t e = hipSetDevice(dev);
-    if (e != hipSuccess)
-        return hip_fail(e, "hipSetDevice");
-    const hhmm_data &d = req->data;
-    const hhmm_draws &w = req->draws;
-    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max, K = (size_t)d.K;
-    const bool gauss = req->model == HHMM_MODEL_HMM_GAUSS;
-    const size_t L = gauss ? 0 : (size_t)d.L;
-    const size_t P = (size_t)npairs(req);
-    hhmm_request dr = *req;
-    hhmm_estep_result dq{};
-    struct Arr {
-        const void *host_in;
-        void *host_out;
-        void **dev;
-        size_t bytes;
-    } arrs[] = {
-        {d.T, nullptr, (void **)&dr.data.T, d.T ? N * 4 : 0},
-        {gauss ? nullptr : d.x_int, nullptr, (void **)&dr.data.x_int, gauss ? 0 : N * Tm * 4},
-        {gauss ? d.x_real : nullptr, nullptr, (void **)&dr.data.x_real, gauss ? N * Tm * 8 : 0},
-        {w.p_1k, nullptr, (void **)&dr.draws.p_1k, S * K * 8},
-        {w.A_ij, nullptr, (void **)&dr.draws.A_ij, S * K * K * 8},
-        {gauss ? nullptr : w.phi_k, nullptr, (void **)&dr.draws.phi_k, S * K * L * 8},
-        {gauss ? w.mu_k : nullptr, nullptr, (void **)&dr.draws.mu_k, gauss ? S * K * 8 : 0},
-        {gauss ? w.sigma_k : nullptr, nullptr, (void **)&dr.draws.sigma_k, gauss ? S * K * 8 : 0},
-        {nullptr, res->loglik, (void **)&dq.loglik, P * 8},
-        {nullptr, res->n_1k, (void **)&dq.n_1k, P * K * 8},
-        {nullptr, res->xi_ij, (void **)&dq.xi_ij, P * K * K * 8},
-        {nullptr, gauss ? nullptr : res->c_kl, (void **)&dq.c_kl, P * K * L * 8},
-        {nullptr, gauss ? res->w_k : nullptr, (void **)&dq.w_k, gauss ? P * K * 8 : 0},
-        {nullptr, gauss ? res->s1_k : nullptr, (void **)&dq.s1_k, gauss ? P * K * 8 : 0},
-        {nullptr, gauss ? res->s2_k : nullptr, (void **)&dq.s2_k, gauss ? P * K * 8 : 0},
-        {nullptr, res->pair_status, (void **)&dq.pair_status, res->pair_status ? P * 4 : 0},
-    };
-    /* one pooled block: every array at a 256-byte boundary, then the workspace */
-    size_t total = 0;
-    std::vector<size_t> off;
-    for (const Arr &a : arrs) {
-        off.push_back(total);
-        if ((a.host_in || a.host_out) && a.bytes)
-            total += (a.bytes + 255) & ~(size_t)255;
-    }
-    const size_t wsb = estep_workspace_bytes(d.K, d.T_max, (int64_t)P);
-    char *blk = (char *)pool_get(dev, total);
-    void *ws = pool_get(dev, wsb);
-    auto cleanup = [&]() {
-        pool_put(blk);
-        pool_put(ws);
-    };
-    if (!blk || !ws) {
-        cleanup();
-        set_error("device %d: E-step allocation of %zu + %zu bytes failed", dev, total, wsb);
-        return HHMM_ERR_OUT_OF_MEMORY;
-    }
-    for (size_t i = 0; i < sizeof(arrs) / sizeof(arrs[0]) && e == hipSuccess; ++i) {
-        const Arr &a = arrs[i];
-        const bool used = (a.host_in || a.host_out) && a.bytes;
-        *a.dev = used ? (void *)(blk + off[i]) : nullptr;
-        if (used && a.host_in)
-            e = hipMemcpy(*a.dev, a.host_in, a.bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        cleanup();
-        return hip_fail(e, "E-step upload");
-    }
-    s = launch_estep(&dr, &dq, (int64_t)P, ws, nullptr);
-    e = hipStreamSynchronize(nullptr); /* before the pooled blocks can go to another request */
-    if (s == HHMM_OK && e == hipSuccess)
-        for (const Arr &a : arrs)
-            if (a.host_out && a.bytes && e == hipSuccess)
-                e = hipMemcpy(a.host_out, *a.dev, a.bytes, hipMemcpyDeviceToHost);
-    cleanup();
-    if (s != HHMM_OK)
-        return s;
-    if (e != hipSuccess)
-        return hip_fail(e, "E-step (kernel execution or download)");
-    return HHMM_OK;
-}
-
-} // extern "C"
-
-/* ------------------------------------------------------------------ */
-/* Draw statistics entry points (include/hhmm_gibbs.h)                  */
-/* ------------------------------------------------------------------ */
-
-/* Argument checks of both entries, none of which needs a device: the entry's
- * own scope and the uniforms first, then the request as hhmm_run /
- * hhmm_run_device check it (host: the data-block bounds too). */
-static hhmm_status draw_stats_check(const hhmm_request *req, const hhmm_estep_result *res, bool host)
-{
-    hhmm_status s = check_draw_stats(req, res);
-    if (s != HHMM_OK)
-        return s;
-    hhmm_request r2 = *req; /* outputs and hat_rand are ignored */
-    r2.outputs = HHMM_OUT_LOGLIK;
-    r2.hat_rand = nullptr;
-    return validate_impl(&r2, nullptr, host);
-}
-
-extern "C" {
+hhmm_status hhmm_estep(const hhmm_request *req, hhmm_estep_result *res) { return stats_host(kEstep, req, res); }
 
 hhmm_status hhmm_draw_stats_workspace_size(const hhmm_request *req, size_t *bytes)
 {
-    if (!req || !bytes) {
-        set_error("NULL argument");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    const int64_t P = npairs(req);
-    if (P < 1 || req->data.K < 1 || req->data.T_max < 1) {
-        set_error("request describes no pairs");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (req->data.K > kMaxK) {
-        set_error("draw statistics: K = %d, the lane-per-pair kernel supports K <= %d", req->data.K, kMaxK);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    *bytes = estep_workspace_bytes(req->data.K, req->data.T_max, P);
-    return HHMM_OK;
+    return stats_workspace_size(kDrawStats, req, bytes);
 }
-
 hhmm_status hhmm_draw_stats_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
                                    size_t workspace_bytes_, void *stream)
 {
-    hhmm_status s = draw_stats_check(req, res, false);
-    if (s != HHMM_OK)
-        return s;
-    if ((s = check_device()) != HHMM_OK)
-        return s;
-    const int64_t P = npairs(req);
-    const size_t need = estep_workspace_bytes(req->data.K, req->data.T_max, P);
-    if (workspace_bytes_ < need || !workspace) {
-        set_error("workspace of %zu bytes < %zu required", workspace_bytes_, need);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    return launch_draw_stats(req, res, P, workspace, (hipStream_t)stream);
+    return stats_device(kDrawStats, req, res, workspace, workspace_bytes_, stream);
 }
-
 hhmm_status hhmm_draw_stats(const hhmm_request *req, hhmm_estep_result *res)
 {
-    hhmm_status s = draw_stats_check(req, res, true);
-    if (s != HHMM_OK)
-        return s;
-    if ((s = check_device()) != HHMM_OK)
-        return s;
-    int dev = req->device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess)
-        return hip_fail(hipGetLastError(), "hipGetDevice");
-    hipError_t e = hipSetDevice(dev);
-    if (e != hipSuccess)
-        return hip_fail(e, "hipSetDevice");
-    const hhmm_data &d = req->data;
-    const hhmm_draws &w = req->draws;
-    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max, K = (size_t)d.K;
-    const size_t L = (size_t)d.L;
-    const size_t P = (size_t)npairs(req);
-    const bool tayal = req->model == HHMM_MODEL_TAYAL;
-    const bool semisup = req->model == HHMM_MODEL_HMM_MULTINOM_SEMISUP;
-    hhmm_request dr = *req;
-    hhmm_estep_result dq{};
-    struct Arr {
-        const void *host_in;
-        void *host_out;
-        void **dev;
-        size_t bytes;
-    } arrs[] = {
-        {d.T, nullptr, (void **)&dr.data.T, d.T ? N * 4 : 0},
-        {d.x_int, nullptr, (void **)&dr.data.x_int, N * Tm * 4},
-        {semisup ? d.g : nullptr, nullptr, (void **)&dr.data.g, semisup ? N * Tm * 4 : 0},
-        {tayal ? d.sign : nullptr, nullptr, (void **)&dr.data.sign, tayal ? N * Tm * 4 : 0},
-        {tayal ? nullptr : w.p_1k, nullptr, (void **)&dr.draws.p_1k, tayal ? 0 : S * K * 8},
-        {tayal ? nullptr : w.A_ij, nullptr, (void **)&dr.draws.A_ij, tayal ? 0 : S * K * K * 8},
-        {tayal ? w.p_11 : nullptr, nullptr, (void **)&dr.draws.p_11, tayal ? S * 8 : 0},
-        {tayal ? w.A_row : nullptr, nullptr, (void **)&dr.draws.A_row, tayal ? S * 4 * 8 : 0},
-        {w.phi_k, nullptr, (void **)&dr.draws.phi_k, S * K * L * 8},
-        {req->ffbs_u, nullptr, (void **)&dr.ffbs_u, P * Tm * 8},
-        {nullptr, res->loglik, (void **)&dq.loglik, P * 8},
-        {nullptr, res->n_1k, (void **)&dq.n_1k, P * K * 8},
-        {nullptr, res->xi_ij, (void **)&dq.xi_ij, P * K * K * 8},
-        {nullptr, res->c_kl, (void **)&dq.c_kl, P * K * L * 8},
-        {nullptr, res->pair_status, (void **)&dq.pair_status, res->pair_status ? P * 4 : 0},
-    };
-    /* one pooled block: every array at a 256-byte boundary, then the workspace */
-    size_t total = 0;
-    std::vector<size_t> off;
-    for (const Arr &a : arrs) {
-        off.push_back(total);
-        if ((a.host_in || a.host_out) && a.bytes)
-            total += (a.bytes + 255) & ~(size_t)255;
-    }
-    const size_t wsb = estep_workspace_bytes(d.K, d.T_max, (int64_t)P);
-    char *blk = (char *)pool_get(dev, total);
-    void *ws = pool_get(dev, wsb);
-    auto cleanup = [&]() {
-        pool_put(blk);
-        pool_put(ws);
-    };
-    if (!blk || !ws) {
-        cleanup();
-        set_error("device %d: draw statistics allocation of %zu + %zu bytes failed", dev, total, wsb);
-        return HHMM_ERR_OUT_OF_MEMORY;
-    }
-    for (size_t i = 0; i < sizeof(arrs) / sizeof(arrs[0]) && e == hipSuccess; ++i) {
-        const Arr &a = arrs[i];
-        const bool used = (a.host_in || a.host_out) && a.bytes;
-        *a.dev = used ? (void *)(blk + off[i]) : nullptr;
-        if (used && a.host_in)
-            e = hipMemcpy(*a.dev, a.host_in, a.bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        cleanup();
-        return hip_fail(e, "draw statistics upload");
-    }
-    s = launch_draw_stats(&dr, &dq, (int64_t)P, ws, nullptr);
-    e = hipStreamSynchronize(nullptr); /* before the pooled blocks can go to another request */
-    if (s == HHMM_OK && e == hipSuccess)
-        for (const Arr &a : arrs)
-            if (a.host_out && a.bytes && e == hipSuccess)
-                e = hipMemcpy(a.host_out, *a.dev, a.bytes, hipMemcpyDeviceToHost);
-    cleanup();
-    if (s != HHMM_OK)
-        return s;
-    if (e != hipSuccess)
-        return hip_fail(e, "draw statistics (kernel execution or download)");
-    return HHMM_OK;
+    return stats_host(kDrawStats, req, res);
 }
-
-} // extern "C"
-
-/* ------------------------------------------------------------------ */
-/* Gaussian draw statistics entry points (include/hhmm_gibbs_gauss.h)   */
-/* ------------------------------------------------------------------ */
-
-/* Argument checks of both entries, none of which needs a device: the entry's
- * own scope and the uniforms first, then the request as hhmm_run /
- * hhmm_run_device check it for hmm (host: the data-block bounds too). */
-static hhmm_status draw_stats_gauss_check(const hhmm_request *req, const hhmm_estep_result *res, bool host)
-{
-    hhmm_status s = check_draw_stats_gauss(req, res);
-    if (s != HHMM_OK)
-        return s;
-    hhmm_request r2 = *req; /* outputs and hat_rand are ignored */
-    r2.outputs = HHMM_OUT_LOGLIK;
-    r2.hat_rand = nullptr;
-    return validate_impl(&r2, nullptr, host);
-}
-
-extern "C" {
 
 hhmm_status hhmm_draw_stats_gauss_workspace_size(const hhmm_request *req, size_t *bytes)
 {
-    if (!req || !bytes) {
-        set_error("NULL argument");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    const int64_t P = npairs(req);
-    if (P < 1 || req->data.K < 1 || req->data.T_max < 1) {
-        set_error("request describes no pairs");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (req->data.K > kMaxK) {
-        set_error("Gaussian draw statistics: K = %d, the lane-per-pair kernel supports K <= %d", req->data.K, kMaxK);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    *bytes = estep_workspace_bytes(req->data.K, req->data.T_max, P);
-    return HHMM_OK;
+    return stats_workspace_size(kDrawStatsGauss, req, bytes);
 }
-
 hhmm_status hhmm_draw_stats_gauss_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
                                          size_t workspace_bytes_, void *stream)
 {
-    hhmm_status s = draw_stats_gauss_check(req, res, false);
-    if (s != HHMM_OK)
-        return s;
-    if ((s = check_device()) != HHMM_OK)
-        return s;
-    const int64_t P = npairs(req);
-    const size_t need = estep_workspace_bytes(req->data.K, req->data.T_max, P);
-    if (workspace_bytes_ < need || !workspace) {
-        set_error("workspace of %zu bytes < %zu required", workspace_bytes_, need);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    return launch_draw_stats_gauss(req, res, P, workspace, (hipStream_t)stream);
+    return stats_device(kDrawStatsGauss, req, res, workspace, workspace_bytes_, stream);
 }
-
 hhmm_status hhmm_draw_stats_gauss(const hhmm_request *req, hhmm_estep_result *res)
 {
-    hhmm_status s = draw_stats_gauss_check(req, res, true);
-    if (s != HHMM_OK)
-        return s;
-    if ((s = check_device()) != HHMM_OK)
-        return s;
-    int dev = req->device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess)
-        return hip_fail(hipGetLastError(), "hipGetDevice");
-    hipError_t e = hipSetDevice(dev);
-    if (e != hipSuccess)
-        return hip_fail(e, "hipSetDevice");
-    const hhmm_data &d = req->data;
-    const hhmm_draws &w = req->draws;
-    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max, K = (size_t)d.K;
-    const size_t P = (size_t)npairs(req);
-    hhmm_request dr = *req;
-    hhmm_estep_result dq{};
-    struct Arr {
-        const void *host_in;
-        void *host_out;
-        void **dev;
-        size_t bytes;
-    } arrs[] = {
-        {d.T, nullptr, (void **)&dr.data.T, d.T ? N * 4 : 0},
-        {d.x_real, nullptr, (void **)&dr.data.x_real, N * Tm * 8},
-        {w.p_1k, nullptr, (void **)&dr.draws.p_1k, S * K * 8},
-        {w.A_ij, nullptr, (void **)&dr.draws.A_ij, S * K * K * 8},
-        {w.mu_k, nullptr, (void **)&dr.draws.mu_k, S * K * 8},
-        {w.sigma_k, nullptr, (void **)&dr.draws.sigma_k, S * K * 8},
-        {req->ffbs_u, nullptr, (void **)&dr.ffbs_u, P * Tm * 8},
-        {nullptr, res->loglik, (void **)&dq.loglik, P * 8},
-        {nullptr, res->n_1k, (void **)&dq.n_1k, P * K * 8},
-        {nullptr, res->xi_ij, (void **)&dq.xi_ij, P * K * K * 8},
-        {nullptr, res->w_k, (void **)&dq.w_k, P * K * 8},
-        {nullptr, res->s1_k, (void **)&dq.s1_k, P * K * 8},
-        {nullptr, res->s2_k, (void **)&dq.s2_k, P * K * 8},
-        {nullptr, res->pair_status, (void **)&dq.pair_status, res->pair_status ? P * 4 : 0},
-    };
-    /* one pooled block: every array at a 256-byte boundary, then the workspace */
-    size_t total = 0;
-    std::vector<size_t> off;
-    for (const Arr &a : arrs) {
-        off.push_back(total);
-        if ((a.host_in || a.host_out) && a.bytes)
-            total += (a.bytes + 255) & ~(size_t)255;
-    }
-    const size_t wsb = estep_workspace_bytes(d.K, d.T_max, (int64_t)P);
-    char *blk = (char *)pool_get(dev, total);
-    void *ws = pool_get(dev, wsb);
-    auto cleanup = [&]() {
-        pool_put(blk);
-        pool_put(ws);
-    };
-    if (!blk || !ws) {
-        cleanup();
-        set_error("device %d: Gaussian draw statistics allocation of %zu + %zu bytes failed", dev, total, wsb);
-        return HHMM_ERR_OUT_OF_MEMORY;
-    }
-    for (size_t i = 0; i < sizeof(arrs) / sizeof(arrs[0]) && e == hipSuccess; ++i) {
-        const Arr &a = arrs[i];
-        const bool used = (a.host_in || a.host_out) && a.bytes;
-        *a.dev = used ? (void *)(blk + off[i]) : nullptr;
-        if (used && a.host_in)
-            e = hipMemcpy(*a.dev, a.host_in, a.bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        cleanup();
-        return hip_fail(e, "Gaussian draw statistics upload");
-    }
-    s = launch_draw_stats_gauss(&dr, &dq, (int64_t)P, ws, nullptr);
-    e = hipStreamSynchronize(nullptr); /* before the pooled blocks can go to another request */
-    if (s == HHMM_OK && e == hipSuccess)
-        for (const Arr &a : arrs)
-            if (a.host_out && a.bytes && e == hipSuccess)
-                e = hipMemcpy(a.host_out, *a.dev, a.bytes, hipMemcpyDeviceToHost);
-    cleanup();
-    if (s != HHMM_OK)
-        return s;
-    if (e != hipSuccess)
-        return hip_fail(e, "Gaussian draw statistics (kernel execution or download)");
-    return HHMM_OK;
+    return stats_host(kDrawStatsGauss, req, res);
 }
-
-} // extern "C"
-
-/* ------------------------------------------------------------------ */
-/* Expected draw statistics entry points (include/hhmm_expect.h)        */
-/* ------------------------------------------------------------------ */
-
-/* Argument checks of both entries, none of which needs a device: the entry's
- * own scope first, then the request as hhmm_run / hhmm_run_device check it
- * (host: the data-block bounds too). */
-static hhmm_status expected_stats_check(const hhmm_request *req, const hhmm_estep_result *res, bool host)
-{
-    hhmm_status s = check_expected_stats(req, res);
-    if (s != HHMM_OK)
-        return s;
-    hhmm_request r2 = *req; /* outputs, ffbs_u and hat_rand are ignored */
-    r2.outputs = HHMM_OUT_LOGLIK;
-    r2.ffbs_u = nullptr;
-    r2.hat_rand = nullptr;
-    return validate_impl(&r2, nullptr, host);
-}
-
-extern "C" {
 
 hhmm_status hhmm_expected_stats_workspace_size(const hhmm_request *req, size_t *bytes)
 {
-    if (!req || !bytes) {
-        set_error("NULL argument");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    const int64_t P = npairs(req);
-    if (P < 1 || req->data.K < 1 || req->data.T_max < 1) {
-        set_error("request describes no pairs");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (req->data.K > kMaxK) {
-        set_error("expected statistics: K = %d, the lane-per-pair kernel supports K <= %d", req->data.K, kMaxK);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    *bytes = estep_workspace_bytes(req->data.K, req->data.T_max, P);
-    return HHMM_OK;
+    return stats_workspace_size(kExpectedStats, req, bytes);
 }
-
 hhmm_status hhmm_expected_stats_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
                                        size_t workspace_bytes_, void *stream)
 {
-    hhmm_status s = expected_stats_check(req, res, false);
-    if (s != HHMM_OK)
-        return s;
-    if ((s = check_device()) != HHMM_OK)
-        return s;
-    const int64_t P = npairs(req);
-    const size_t need = estep_workspace_bytes(req->data.K, req->data.T_max, P);
-    if (workspace_bytes_ < need || !workspace) {
-        set_error("workspace of %zu bytes < %zu required", workspace_bytes_, need);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    return launch_expected_stats(req, res, P, workspace, (hipStream_t)stream);
+    return stats_device(kExpectedStats, req, res, workspace, workspace_bytes_, stream);
 }
-
 hhmm_status hhmm_expected_stats(const hhmm_request *req, hhmm_estep_result *res)
 {
-    hhmm_status s = expected_stats_check(req, res, true);
-    if (s != HHMM_OK)
-        return s;
-    if ((s = check_device()) != HHMM_OK)
-        return s;
-    int dev = req->device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess)
-        return hip_fail(hipGetLastError(), "hipGetDevice");
-    hipError_t e = hipSetDevice(dev);
-    if (e != hipSuccess)
-        return hip_fail(e, "hipSetDevice");
-    const hhmm_data &d = req->data;
-    const hhmm_draws &w = req->draws;
-    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max, K = (size_t)d.K;
-    const size_t L = (size_t)d.L;
-    const size_t P = (size_t)npairs(req);
-    const bool tayal = req->model == HHMM_MODEL_TAYAL;
-    const bool semisup = req->model == HHMM_MODEL_HMM_MULTINOM_SEMISUP;
-    hhmm_request dr = *req;
-    hhmm_estep_result dq{};
-    struct Arr {
-        const void *host_in;
-        void *host_out;
-        void **dev;
-        size_t bytes;
-    } arrs[] = {
-        {d.T, nullptr, (void **)&dr.data.T, d.T ? N * 4 : 0},
-        {d.x_int, nullptr, (void **)&dr.data.x_int, N * Tm * 4},
-        {semisup ? d.g : nullptr, nullptr, (void **)&dr.data.g, semisup ? N * Tm * 4 : 0},
-        {tayal ? d.sign : nullptr, nullptr, (void **)&dr.data.sign, tayal ? N * Tm * 4 : 0},
-        {tayal ? nullptr : w.p_1k, nullptr, (void **)&dr.draws.p_1k, tayal ? 0 : S * K * 8},
-        {tayal ? nullptr : w.A_ij, nullptr, (void **)&dr.draws.A_ij, tayal ? 0 : S * K * K * 8},
-        {tayal ? w.p_11 : nullptr, nullptr, (void **)&dr.draws.p_11, tayal ? S * 8 : 0},
-        {tayal ? w.A_row : nullptr, nullptr, (void **)&dr.draws.A_row, tayal ? S * 4 * 8 : 0},
-        {w.phi_k, nullptr, (void **)&dr.draws.phi_k, S * K * L * 8},
-        {nullptr, res->loglik, (void **)&dq.loglik, P * 8},
-        {nullptr, res->n_1k, (void **)&dq.n_1k, P * K * 8},
-        {nullptr, res->xi_ij, (void **)&dq.xi_ij, P * K * K * 8},
-        {nullptr, res->c_kl, (void **)&dq.c_kl, P * K * L * 8},
-        {nullptr, res->pair_status, (void **)&dq.pair_status, res->pair_status ? P * 4 : 0},
-    };
-    /* one pooled block: every array at a 256-byte boundary, then the workspace */
-    size_t total = 0;
-    std::vector<size_t> off;
-    for (const Arr &a : arrs) {
-        off.push_back(total);
-        if ((a.host_in || a.host_out) && a.bytes)
-            total += (a.bytes + 255) & ~(size_t)255;
-    }
-    const size_t wsb = estep_workspace_bytes(d.K, d.T_max, (int64_t)P);
-    char *blk = (char *)pool_get(dev, total);
-    void *ws = pool_get(dev, wsb);
-    auto cleanup = [&]() {
-        pool_put(blk);
-        pool_put(ws);
-    };
-    if (!blk || !ws) {
-        cleanup();
-        set_error("device %d: expected statistics allocation of %zu + %zu bytes failed", dev, total, wsb);
-        return HHMM_ERR_OUT_OF_MEMORY;
-    }
-    for (size_t i = 0; i < sizeof(arrs) / sizeof(arrs[0]) && e == hipSuccess; ++i) {
-        const Arr &a = arrs[i];
-        const bool used = (a.host_in || a.host_out) && a.bytes;
-        *a.dev = used ? (void *)(blk + off[i]) : nullptr;
-        if (used && a.host_in)
-            e = hipMemcpy(*a.dev, a.host_in, a.bytes, hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        cleanup();
-        return hip_fail(e, "expected statistics upload");
-    }
-    s = launch_expected_stats(&dr, &dq, (int64_t)P, ws, nullptr);
-    e = hipStreamSynchronize(nullptr); /* before the pooled blocks can go to another request */
-    if (s == HHMM_OK && e == hipSuccess)
-        for (const Arr &a : arrs)
-            if (a.host_out && a.bytes && e == hipSuccess)
-                e = hipMemcpy(a.host_out, *a.dev, a.bytes, hipMemcpyDeviceToHost);
-    cleanup();
-    if (s != HHMM_OK)
-        return s;
-    if (e != hipSuccess)
-        return hip_fail(e, "expected statistics (kernel execution or download)");
-    return HHMM_OK;
+    return stats_host(kExpectedStats, req, res);
 }
 
 } // extern "C"

@@ -32,6 +32,7 @@
 #include "hhmm_gibbs.h"
 #include "hhmm_hmm.h"
 #include "hhmm_drawstep.h"
+#include "hhmm_stats.h"
 
 namespace hhmm {
 
@@ -259,15 +260,7 @@ static size_t draw_stats_wave_lds(int K, int L)
 }
 
 /* Waves per workgroup and its LDS. */
-static int draw_stats_waves(int K, int L, size_t *lds)
-{
-    const size_t per_wave = draw_stats_wave_lds(K, L);
-    int waves = kBlock / 64;
-    while (waves > 0 && per_wave * waves > kLdsLimit)
-        --waves;
-    *lds = per_wave * waves;
-    return waves;
-}
+static int draw_stats_waves(int K, int L, size_t *lds) { return waves_that_fit(draw_stats_wave_lds(K, L), lds); }
 
 static bool draw_stats_model(int m)
 {
@@ -276,32 +269,11 @@ static bool draw_stats_model(int m)
 
 hhmm_status check_draw_stats(const hhmm_request *r, const hhmm_estep_result *o)
 {
-    if (!r) {
-        set_error("request must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->abi_version != HHMM_ABI_VERSION) {
-        set_error("abi_version %u != %u", r->abi_version, HHMM_ABI_VERSION);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->model < 1 || r->model > 9) {
-        set_error("unknown model id %d", r->model);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (!draw_stats_model(r->model)) {
-        set_error("draw statistics: model %d is not supported (hmm-multinom, hmm-multinom-semisup and hhmm-tayal2009 "
-                  "only; the Gaussian hmm has its own entry, hhmm_draw_stats_gauss)",
-                  r->model);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    if (r->data.K > kMaxK) {
-        set_error("draw statistics: K = %d, the lane-per-pair kernel supports K <= %d", r->data.K, kMaxK);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    if (r->device == HHMM_DEVICE_SET) {
-        set_error("draw statistics: HHMM_DEVICE_SET is not supported (one device per call)");
-        return HHMM_ERR_UNSUPPORTED;
-    }
+    const hhmm_status s = stats_check_head("draw statistics", r, draw_stats_model,
+                                           "hmm-multinom, hmm-multinom-semisup and hhmm-tayal2009 only; the Gaussian "
+                                           "hmm has its own entry, hhmm_draw_stats_gauss");
+    if (s != HHMM_OK)
+        return s;
     if (r->data.K >= 1 && r->data.L >= 1) {
         size_t lds;
         if (draw_stats_waves(r->data.K, r->data.L, &lds) < 1) {
@@ -311,19 +283,7 @@ hhmm_status check_draw_stats(const hhmm_request *r, const hhmm_estep_result *o)
             return HHMM_ERR_UNSUPPORTED;
         }
     }
-    if (!o) {
-        set_error("draw statistics result must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (!o->loglik || !o->n_1k || !o->xi_ij || !o->c_kl) {
-        set_error("draw statistics: loglik, n_1k, xi_ij and c_kl must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (!r->ffbs_u) {
-        set_error("draw statistics: ffbs_u (the [P, T_max] uniforms of the draw) must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    return HHMM_OK;
+    return stats_check_tail("draw statistics", r, o, true);
 }
 
 template <int MODEL, int K>
@@ -337,42 +297,21 @@ template <int MODEL>
 static bool launch_draw_stats_m(const DevArgs &a, const DrawStatsOut &o, dim3 grid, dim3 block, size_t lds,
                                 hipStream_t st)
 {
-    switch (a.K) {
-    case 1: launch_draw_stats_k<MODEL, 1>(a, o, grid, block, lds, st); return true;
-    case 2: launch_draw_stats_k<MODEL, 2>(a, o, grid, block, lds, st); return true;
-    case 3: launch_draw_stats_k<MODEL, 3>(a, o, grid, block, lds, st); return true;
-    case 4: launch_draw_stats_k<MODEL, 4>(a, o, grid, block, lds, st); return true;
-    case 5: launch_draw_stats_k<MODEL, 5>(a, o, grid, block, lds, st); return true;
-    case 6: launch_draw_stats_k<MODEL, 6>(a, o, grid, block, lds, st); return true;
-    case 7: launch_draw_stats_k<MODEL, 7>(a, o, grid, block, lds, st); return true;
-    case 8: launch_draw_stats_k<MODEL, 8>(a, o, grid, block, lds, st); return true;
-    default: return false;
-    }
+    return dispatch_k(a.K, [&](auto kc) {
+        launch_draw_stats_k<MODEL, decltype(kc)::value>(a, o, grid, block, lds, st);
+    });
 }
 
 hhmm_status launch_draw_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws, hipStream_t st)
 {
-    DevArgs a{};
-    a.P = P;
-    a.N = r->data.n_series;
-    a.S = r->draws.n_draws;
-    a.pairing = r->pairing;
-    a.model = r->model;
-    a.K = r->data.K;
-    a.L = r->data.L;
-    a.Tmax = r->data.T_max;
-    a.Tout = r->data.T_max;
-    a.T = r->data.T;
+    DevArgs a = stats_dev_args(r, P, ws);
     a.x = r->data.x_int;
     a.g = r->data.g;
     a.sign = r->data.sign;
-    a.p_1k = r->draws.p_1k;
-    a.A_ij = r->draws.A_ij;
     a.phi_k = r->draws.phi_k;
     a.p_11 = r->draws.p_11;
     a.A_row = r->draws.A_row;
     a.ffbs_u = r->ffbs_u;
-    a.ckpt = (double *)ws;
     DrawStatsOut o{res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->pair_status};
     size_t lds = 0;
     const int waves = draw_stats_waves(a.K, a.L, &lds);
@@ -395,12 +334,7 @@ hhmm_status launch_draw_stats(const hhmm_request *r, const hhmm_estep_result *re
         set_error("draw statistics: model %d at K = %d has no kernel (K outside 1..%d)", a.model, a.K, kMaxK);
         return HHMM_ERR_UNSUPPORTED;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("draw_stats_kernel launch: %s", hipGetErrorString(e));
-        return HHMM_ERR_HIP;
-    }
-    return HHMM_OK;
+    return launch_status("draw_stats_kernel");
 }
 
 } // namespace hhmm

@@ -34,6 +34,7 @@
 #include "hhmm_gibbs_gauss.h"
 #include "hhmm_hmm.h"
 #include "hhmm_drawstep.h"
+#include "hhmm_stats.h"
 
 namespace hhmm {
 
@@ -277,77 +278,26 @@ static int draw_stats_gauss_waves(int K, size_t *lds)
     return best;
 }
 
+static bool draw_stats_gauss_model(int m) { return m == HHMM_MODEL_HMM_GAUSS; }
+
 hhmm_status check_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_result *o)
 {
-    if (!r) {
-        set_error("request must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->abi_version != HHMM_ABI_VERSION) {
-        set_error("abi_version %u != %u", r->abi_version, HHMM_ABI_VERSION);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->model < 1 || r->model > 9) {
-        set_error("unknown model id %d", r->model);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->model != HHMM_MODEL_HMM_GAUSS) {
-        set_error("Gaussian draw statistics: model %d is not supported (hmm only; the discrete programs go to "
-                  "hhmm_draw_stats)",
-                  r->model);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    if (r->data.K > kMaxK) {
-        set_error("Gaussian draw statistics: K = %d, the lane-per-pair kernel supports K <= %d", r->data.K, kMaxK);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    if (r->device == HHMM_DEVICE_SET) {
-        set_error("Gaussian draw statistics: HHMM_DEVICE_SET is not supported (one device per call)");
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    if (!o) {
-        set_error("Gaussian draw statistics result must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (!o->loglik || !o->n_1k || !o->xi_ij || !o->w_k || !o->s1_k || !o->s2_k) {
-        set_error("Gaussian draw statistics: loglik, n_1k, xi_ij, w_k, s1_k and s2_k must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (!r->ffbs_u) {
-        set_error("Gaussian draw statistics: ffbs_u (the [P, T_max] uniforms of the draw) must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    return HHMM_OK;
-}
-
-template <int K>
-static void launch_draw_stats_gauss_k(const DevArgs &a, const DrawStatsGaussOut &o, dim3 grid, dim3 block, size_t lds,
-                                      hipStream_t st)
-{
-    hipLaunchKernelGGL((draw_stats_gauss_kernel<K>), grid, block, lds, st, a, o);
+    const hhmm_status s = stats_check_head("Gaussian draw statistics", r, draw_stats_gauss_model,
+                                           "hmm only; the discrete programs go to hhmm_draw_stats");
+    if (s != HHMM_OK) /* the tables of every K <= kMaxK fit in LDS */
+        return s;
+    return stats_check_tail("Gaussian draw statistics", r, o, true);
 }
 
 hhmm_status launch_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                                     hipStream_t st)
 {
-    DevArgs a{};
-    a.P = P;
-    a.N = r->data.n_series;
-    a.S = r->draws.n_draws;
-    a.pairing = r->pairing;
-    a.model = r->model;
-    a.K = r->data.K;
+    DevArgs a = stats_dev_args(r, P, ws);
     a.L = 0;
-    a.Tmax = r->data.T_max;
-    a.Tout = r->data.T_max;
-    a.T = r->data.T;
     a.xr = r->data.x_real;
-    a.p_1k = r->draws.p_1k;
-    a.A_ij = r->draws.A_ij;
     a.mu_k = r->draws.mu_k;
     a.sigma_k = r->draws.sigma_k;
     a.ffbs_u = r->ffbs_u;
-    a.ckpt = (double *)ws;
     DrawStatsGaussOut o{res->loglik, res->n_1k, res->xi_ij, res->w_k, res->s1_k, res->s2_k, res->pair_status};
     if (a.K < 1 || a.K > kMaxK) {
         set_error("Gaussian draw statistics: K = %d outside 1..%d", a.K, kMaxK);
@@ -356,22 +306,10 @@ hhmm_status launch_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_resu
     size_t lds = 0;
     const int threads = 64 * draw_stats_gauss_waves(a.K, &lds);
     const dim3 grid((unsigned)((P + threads - 1) / threads)), block(threads);
-    switch (a.K) {
-    case 1: launch_draw_stats_gauss_k<1>(a, o, grid, block, lds, st); break;
-    case 2: launch_draw_stats_gauss_k<2>(a, o, grid, block, lds, st); break;
-    case 3: launch_draw_stats_gauss_k<3>(a, o, grid, block, lds, st); break;
-    case 4: launch_draw_stats_gauss_k<4>(a, o, grid, block, lds, st); break;
-    case 5: launch_draw_stats_gauss_k<5>(a, o, grid, block, lds, st); break;
-    case 6: launch_draw_stats_gauss_k<6>(a, o, grid, block, lds, st); break;
-    case 7: launch_draw_stats_gauss_k<7>(a, o, grid, block, lds, st); break;
-    default: launch_draw_stats_gauss_k<8>(a, o, grid, block, lds, st); break;
-    }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("draw_stats_gauss_kernel launch: %s", hipGetErrorString(e));
-        return HHMM_ERR_HIP;
-    }
-    return HHMM_OK;
+    dispatch_k(a.K, [&](auto kc) {
+        hipLaunchKernelGGL((draw_stats_gauss_kernel<decltype(kc)::value>), grid, block, lds, st, a, o);
+    });
+    return launch_status("draw_stats_gauss_kernel");
 }
 
 } // namespace hhmm

@@ -36,6 +36,7 @@
 
 #include "hhmm_estep.h"
 #include "hhmm_hmm.h"
+#include "hhmm_stats.h"
 
 namespace hhmm {
 
@@ -371,17 +372,11 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
 /* Waves per workgroup and its LDS: two slabs per wave for hmm-multinom. */
 static int estep_waves(int model, int K, int L, size_t *lds)
 {
-    *lds = 0;
     if (model == HHMM_MODEL_HMM_GAUSS) { /* K >= 7: xi in LDS (estep_xi_lds) */
         *lds = K >= 7 ? (size_t)(kBlock / 64) * K * K * 64 * sizeof(double) : 0;
         return kBlock / 64;
     }
-    const size_t per_wave = 2 * (size_t)L * (size_t)((K + 1) / 2) * 64 * sizeof(double2);
-    int waves = kBlock / 64;
-    while (waves > 0 && per_wave * waves > kLdsLimit)
-        --waves;
-    *lds = per_wave * waves;
-    return waves;
+    return waves_that_fit(2 * (size_t)L * (size_t)((K + 1) / 2) * 64 * sizeof(double2), lds);
 }
 
 static int64_t estep_chunks(int K, int Tmax) { return ((int64_t)Tmax + fb_chunk(K) - 1) / fb_chunk(K); }
@@ -391,34 +386,15 @@ size_t estep_workspace_bytes(int K, int Tmax, int64_t P)
     return (size_t)estep_chunks(K, Tmax) * (size_t)K * (size_t)P * sizeof(double);
 }
 
+static bool estep_model(int m) { return m == HHMM_MODEL_HMM_GAUSS || m == HHMM_MODEL_HMM_MULTINOM; }
+
 hhmm_status check_estep(const hhmm_request *r, const hhmm_estep_result *o)
 {
-    if (!r) {
-        set_error("request must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->abi_version != HHMM_ABI_VERSION) {
-        set_error("abi_version %u != %u", r->abi_version, HHMM_ABI_VERSION);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->model < 1 || r->model > 9) {
-        set_error("unknown model id %d", r->model);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->model != HHMM_MODEL_HMM_GAUSS && r->model != HHMM_MODEL_HMM_MULTINOM) {
-        set_error("E-step: model %d is not supported (hmm and hmm-multinom only; the semisup and Tayal backward "
-                  "passes are not the adjoint of their forward)",
-                  r->model);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    if (r->data.K > kMaxK) {
-        set_error("E-step: K = %d, the lane-per-pair kernel supports K <= %d", r->data.K, kMaxK);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    if (r->device == HHMM_DEVICE_SET) {
-        set_error("E-step: HHMM_DEVICE_SET is not supported (one device per call)");
-        return HHMM_ERR_UNSUPPORTED;
-    }
+    const hhmm_status s = stats_check_head("E-step", r, estep_model,
+                                           "hmm and hmm-multinom only; the semisup and Tayal backward passes are "
+                                           "not the adjoint of their forward");
+    if (s != HHMM_OK)
+        return s;
     if (r->model == HHMM_MODEL_HMM_MULTINOM && r->data.K >= 1 && r->data.L >= 1) {
         size_t lds;
         if (estep_waves(r->model, r->data.K, r->data.L, &lds) < 1) {
@@ -428,68 +404,25 @@ hhmm_status check_estep(const hhmm_request *r, const hhmm_estep_result *o)
             return HHMM_ERR_UNSUPPORTED;
         }
     }
-    if (!o) {
-        set_error("E-step result must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (!o->loglik || !o->n_1k || !o->xi_ij) {
-        set_error("E-step: loglik, n_1k and xi_ij must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->model == HHMM_MODEL_HMM_MULTINOM && !o->c_kl) {
-        set_error("E-step: hmm-multinom needs c_kl");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->model == HHMM_MODEL_HMM_GAUSS && (!o->w_k || !o->s1_k || !o->s2_k)) {
-        set_error("E-step: hmm needs w_k, s1_k and s2_k");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    return HHMM_OK;
-}
-
-template <int MODEL, int K>
-static void launch_estep_k(const DevArgs &a, const EstepOut &o, dim3 grid, dim3 block, size_t lds, hipStream_t st)
-{
-    hipLaunchKernelGGL((estep_kernel<MODEL, K>), grid, block, lds, st, a, o);
+    return stats_check_tail("E-step", r, o, false);
 }
 
 template <int MODEL>
 static bool launch_estep_m(const DevArgs &a, const EstepOut &o, dim3 grid, dim3 block, size_t lds, hipStream_t st)
 {
-    switch (a.K) {
-    case 1: launch_estep_k<MODEL, 1>(a, o, grid, block, lds, st); return true;
-    case 2: launch_estep_k<MODEL, 2>(a, o, grid, block, lds, st); return true;
-    case 3: launch_estep_k<MODEL, 3>(a, o, grid, block, lds, st); return true;
-    case 4: launch_estep_k<MODEL, 4>(a, o, grid, block, lds, st); return true;
-    case 5: launch_estep_k<MODEL, 5>(a, o, grid, block, lds, st); return true;
-    case 6: launch_estep_k<MODEL, 6>(a, o, grid, block, lds, st); return true;
-    case 7: launch_estep_k<MODEL, 7>(a, o, grid, block, lds, st); return true;
-    case 8: launch_estep_k<MODEL, 8>(a, o, grid, block, lds, st); return true;
-    default: return false;
-    }
+    return dispatch_k(a.K, [&](auto kc) {
+        hipLaunchKernelGGL((estep_kernel<MODEL, decltype(kc)::value>), grid, block, lds, st, a, o);
+    });
 }
 
 hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws, hipStream_t st)
 {
-    DevArgs a{};
-    a.P = P;
-    a.N = r->data.n_series;
-    a.S = r->draws.n_draws;
-    a.pairing = r->pairing;
-    a.model = r->model;
-    a.K = r->data.K;
-    a.L = r->data.L;
-    a.Tmax = r->data.T_max;
-    a.Tout = r->data.T_max;
-    a.T = r->data.T;
+    DevArgs a = stats_dev_args(r, P, ws);
     a.x = r->data.x_int;
     a.xr = r->data.x_real;
-    a.p_1k = r->draws.p_1k;
-    a.A_ij = r->draws.A_ij;
     a.phi_k = r->draws.phi_k;
     a.mu_k = r->draws.mu_k;
     a.sigma_k = r->draws.sigma_k;
-    a.ckpt = (double *)ws;
     EstepOut o{res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->w_k, res->s1_k, res->s2_k, res->pair_status};
     size_t lds = 0;
     const int waves = estep_waves(a.model, a.K, a.L, &lds);
@@ -505,12 +438,7 @@ hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, in
         set_error("E-step: K = %d outside 1..%d", a.K, kMaxK);
         return HHMM_ERR_UNSUPPORTED;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("estep_kernel launch: %s", hipGetErrorString(e));
-        return HHMM_ERR_HIP;
-    }
-    return HHMM_OK;
+    return launch_status("estep_kernel");
 }
 
 } // namespace hhmm

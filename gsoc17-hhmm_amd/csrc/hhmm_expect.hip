@@ -33,6 +33,7 @@
 
 #include "hhmm_expect.h"
 #include "hhmm_hmm.h"
+#include "hhmm_stats.h"
 
 namespace hhmm {
 
@@ -426,12 +427,7 @@ __global__ void __launch_bounds__(kBlock) expect_kernel(const DevArgs a, const E
 /* Waves per workgroup and its LDS: the E-step's two slabs per wave. */
 static int expect_waves(int K, int L, size_t *lds)
 {
-    const size_t per_wave = 2 * (size_t)L * (size_t)((K + 1) / 2) * 64 * sizeof(double2);
-    int waves = kBlock / 64;
-    while (waves > 0 && per_wave * waves > kLdsLimit)
-        --waves;
-    *lds = per_wave * waves;
-    return waves;
+    return waves_that_fit(2 * (size_t)L * (size_t)((K + 1) / 2) * 64 * sizeof(double2), lds);
 }
 
 static bool expect_model(int m)
@@ -441,32 +437,11 @@ static bool expect_model(int m)
 
 hhmm_status check_expected_stats(const hhmm_request *r, const hhmm_estep_result *o)
 {
-    if (!r) {
-        set_error("request must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->abi_version != HHMM_ABI_VERSION) {
-        set_error("abi_version %u != %u", r->abi_version, HHMM_ABI_VERSION);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (r->model < 1 || r->model > 9) {
-        set_error("unknown model id %d", r->model);
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (!expect_model(r->model)) {
-        set_error("expected statistics: model %d is not supported (hmm-multinom, hmm-multinom-semisup and "
-                  "hhmm-tayal2009 only; the Gaussian hmm has hhmm_estep)",
-                  r->model);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    if (r->data.K > kMaxK) {
-        set_error("expected statistics: K = %d, the lane-per-pair kernel supports K <= %d", r->data.K, kMaxK);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    if (r->device == HHMM_DEVICE_SET) {
-        set_error("expected statistics: HHMM_DEVICE_SET is not supported (one device per call)");
-        return HHMM_ERR_UNSUPPORTED;
-    }
+    const hhmm_status s = stats_check_head("expected statistics", r, expect_model,
+                                           "hmm-multinom, hmm-multinom-semisup and hhmm-tayal2009 only; the Gaussian "
+                                           "hmm has hhmm_estep");
+    if (s != HHMM_OK)
+        return s;
     if (r->data.K >= 1 && r->data.L >= 1) {
         size_t lds;
         if (expect_waves(r->data.K, r->data.L, &lds) < 1) {
@@ -476,15 +451,7 @@ hhmm_status check_expected_stats(const hhmm_request *r, const hhmm_estep_result 
             return HHMM_ERR_UNSUPPORTED;
         }
     }
-    if (!o) {
-        set_error("expected statistics result must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    if (!o->loglik || !o->n_1k || !o->xi_ij || !o->c_kl) {
-        set_error("expected statistics: loglik, n_1k, xi_ij and c_kl must be non-NULL");
-        return HHMM_ERR_INVALID_ARGUMENT;
-    }
-    return HHMM_OK;
+    return stats_check_tail("expected statistics", r, o, false);
 }
 
 template <int MODEL, int K>
@@ -493,47 +460,18 @@ static void launch_expect_k(const DevArgs &a, const ExpectOut &o, dim3 grid, dim
     hipLaunchKernelGGL((expect_kernel<MODEL, K>), grid, block, lds, st, a, o);
 }
 
-template <int MODEL>
-static bool launch_expect_m(const DevArgs &a, const ExpectOut &o, dim3 grid, dim3 block, size_t lds, hipStream_t st)
-{
-    switch (a.K) {
-    case 1: launch_expect_k<MODEL, 1>(a, o, grid, block, lds, st); return true;
-    case 2: launch_expect_k<MODEL, 2>(a, o, grid, block, lds, st); return true;
-    case 3: launch_expect_k<MODEL, 3>(a, o, grid, block, lds, st); return true;
-    case 4: launch_expect_k<MODEL, 4>(a, o, grid, block, lds, st); return true;
-    case 5: launch_expect_k<MODEL, 5>(a, o, grid, block, lds, st); return true;
-    case 6: launch_expect_k<MODEL, 6>(a, o, grid, block, lds, st); return true;
-    case 7: launch_expect_k<MODEL, 7>(a, o, grid, block, lds, st); return true;
-    case 8: launch_expect_k<MODEL, 8>(a, o, grid, block, lds, st); return true;
-    default: return false;
-    }
-}
-
 hhmm_status launch_expected_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                                   hipStream_t st)
 {
     if (r->model == HHMM_MODEL_HMM_MULTINOM) /* no mask: the E-step itself */
         return launch_estep(r, res, P, ws, st);
-    DevArgs a{};
-    a.P = P;
-    a.N = r->data.n_series;
-    a.S = r->draws.n_draws;
-    a.pairing = r->pairing;
-    a.model = r->model;
-    a.K = r->data.K;
-    a.L = r->data.L;
-    a.Tmax = r->data.T_max;
-    a.Tout = r->data.T_max;
-    a.T = r->data.T;
+    DevArgs a = stats_dev_args(r, P, ws);
     a.x = r->data.x_int;
     a.g = r->data.g;
     a.sign = r->data.sign;
-    a.p_1k = r->draws.p_1k;
-    a.A_ij = r->draws.A_ij;
     a.phi_k = r->draws.phi_k;
     a.p_11 = r->draws.p_11;
     a.A_row = r->draws.A_row;
-    a.ckpt = (double *)ws;
     ExpectOut o{res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->pair_status,
                 r->model == HHMM_MODEL_TAYAL ? 2 : r->data.G};
     size_t lds = 0;
@@ -546,7 +484,9 @@ hhmm_status launch_expected_stats(const hhmm_request *r, const hhmm_estep_result
     const dim3 grid((unsigned)((P + threads - 1) / threads)), block(threads);
     bool ok = false;
     if (a.model == HHMM_MODEL_HMM_MULTINOM_SEMISUP)
-        ok = launch_expect_m<HHMM_MODEL_HMM_MULTINOM_SEMISUP>(a, o, grid, block, lds, st);
+        ok = dispatch_k(a.K, [&](auto kc) {
+            launch_expect_k<HHMM_MODEL_HMM_MULTINOM_SEMISUP, decltype(kc)::value>(a, o, grid, block, lds, st);
+        });
     else if (a.model == HHMM_MODEL_TAYAL && a.K == 4) {
         launch_expect_k<HHMM_MODEL_TAYAL, 4>(a, o, grid, block, lds, st);
         ok = true;
@@ -555,12 +495,7 @@ hhmm_status launch_expected_stats(const hhmm_request *r, const hhmm_estep_result
         set_error("expected statistics: model %d at K = %d has no kernel (K outside 1..%d)", a.model, a.K, kMaxK);
         return HHMM_ERR_UNSUPPORTED;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("expect_kernel launch: %s", hipGetErrorString(e));
-        return HHMM_ERR_HIP;
-    }
-    return HHMM_OK;
+    return launch_status("expect_kernel");
 }
 
 } // namespace hhmm

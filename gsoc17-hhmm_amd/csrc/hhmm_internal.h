@@ -219,7 +219,11 @@ void set_error(const char *fmt, ...);
 hhmm_status check_summary(const hhmm_summary_request *r, const double *quantiles, const int32_t *argmax);
 hhmm_status launch_summary(const hhmm_summary_request *r, double *quantiles, int32_t *argmax, hipStream_t st);
 
-/* Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
+/* The four "statistics per (series, draw) pair" entries below each give the
+ * host path of hhmm_api.cpp (StatsEntry, stats_*) a check_* and a launch_*;
+ * what those share among themselves is in hhmm_stats.h.
+ *
+ * Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
  * checkpoint workspace and the launch on `st` (device pointers). */
 hhmm_status check_estep(const hhmm_request *r, const hhmm_estep_result *o);
 size_t estep_workspace_bytes(int K, int Tmax, int64_t P);

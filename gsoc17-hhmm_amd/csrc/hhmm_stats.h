@@ -1,0 +1,128 @@
+/*
+ * hhmm_stats.h -- host-side pieces shared by the four "statistics per
+ * (series, draw) pair" entries: the E-step (hhmm_estep.hip), the draw
+ * statistics (hhmm_draw_stats.hip, hhmm_draw_stats_gauss.hip) and the expected
+ * draw statistics (hhmm_expect.hip).  The kernels differ; the argument checks,
+ * the DevArgs of a launch, the LDS fit, the dispatch on K and the launch
+ * epilogue do not.  Not part of the public ABI.
+ */
+#pragma once
+#include <type_traits>
+
+#include "hhmm_internal.h"
+
+namespace hhmm {
+
+/* Head of an entry's check_*, in this order: NULL request, ABI, model id, the
+ * entry's scope (`scope` says which models it takes and where the others go),
+ * K, HHMM_DEVICE_SET.  `entry`: the entry's name in messages. */
+inline hhmm_status stats_check_head(const char *entry, const hhmm_request *r, bool (*model_ok)(int), const char *scope)
+{
+    if (!r) {
+        set_error("%s: request must be non-NULL", entry);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (r->abi_version != HHMM_ABI_VERSION) {
+        set_error("%s: abi_version %u != %u", entry, r->abi_version, HHMM_ABI_VERSION);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (r->model < 1 || r->model > 9) {
+        set_error("%s: unknown model id %d", entry, r->model);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (!model_ok(r->model)) {
+        set_error("%s: model %d is not supported (%s)", entry, r->model, scope);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if (r->data.K > kMaxK) {
+        set_error("%s: K = %d, the lane-per-pair kernel supports K <= %d", entry, r->data.K, kMaxK);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if (r->device == HHMM_DEVICE_SET) {
+        set_error("%s: HHMM_DEVICE_SET is not supported (one device per call)", entry);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    return HHMM_OK;
+}
+
+/* Tail of an entry's check_*, after its LDS-fit test: NULL result, the outputs
+ * of the model's emission family, and the uniforms where the entry reads them. */
+inline hhmm_status stats_check_tail(const char *entry, const hhmm_request *r, const hhmm_estep_result *o, bool reads_u)
+{
+    if (!o) {
+        set_error("%s: result must be non-NULL", entry);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    const bool gauss = r->model == HHMM_MODEL_HMM_GAUSS;
+    if (!o->loglik || !o->n_1k || !o->xi_ij || (gauss ? !o->w_k || !o->s1_k || !o->s2_k : !o->c_kl)) {
+        set_error("%s: loglik, n_1k, xi_ij and %s must be non-NULL", entry, gauss ? "w_k, s1_k and s2_k" : "c_kl");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    if (reads_u && !r->ffbs_u) {
+        set_error("%s: ffbs_u (the [P, T_max] uniforms of the draw) must be non-NULL", entry);
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    return HHMM_OK;
+}
+
+/* The DevArgs fields every entry takes from the request; the data and draw
+ * arrays of its own model family are explicit lines at the call site. */
+inline DevArgs stats_dev_args(const hhmm_request *r, int64_t P, void *ws)
+{
+    DevArgs a{};
+    a.P = P;
+    a.N = r->data.n_series;
+    a.S = r->draws.n_draws;
+    a.pairing = r->pairing;
+    a.model = r->model;
+    a.K = r->data.K;
+    a.L = r->data.L;
+    a.Tmax = r->data.T_max;
+    a.Tout = r->data.T_max;
+    a.T = r->data.T;
+    a.p_1k = r->draws.p_1k;
+    a.A_ij = r->draws.A_ij;
+    a.ckpt = (double *)ws;
+    return a;
+}
+
+/* Waves per workgroup, at most kBlock / 64, whose tables of per_wave bytes
+ * each fit in LDS together (0: not even one), and the workgroup's LDS. */
+inline int waves_that_fit(size_t per_wave, size_t *lds)
+{
+    int waves = kBlock / 64;
+    while (waves > 0 && per_wave * waves > kLdsLimit)
+        --waves;
+    *lds = per_wave * waves;
+    return waves;
+}
+
+/* f(std::integral_constant<int, K>{}) for K in 1..kMaxK; false: K outside. */
+template <class F>
+bool dispatch_k(int K, F &&f)
+{
+    switch (K) {
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 3: f(std::integral_constant<int, 3>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 5: f(std::integral_constant<int, 5>{}); return true;
+    case 6: f(std::integral_constant<int, 6>{}); return true;
+    case 7: f(std::integral_constant<int, 7>{}); return true;
+    case 8: f(std::integral_constant<int, 8>{}); return true;
+    default: return false;
+    }
+}
+
+/* After a launch: the launch error of `kernel`, if any. */
+inline hhmm_status launch_status(const char *kernel)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error("%s launch: %s", kernel, hipGetErrorString(e));
+        return HHMM_ERR_HIP;
+    }
+    return HHMM_OK;
+}
+
+} // namespace hhmm

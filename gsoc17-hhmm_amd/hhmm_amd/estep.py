@@ -20,12 +20,10 @@ for the two masked programs (FIT_MODELS): hmm-multinom-semisup with the
 hmm-multinom formulas, hhmm-tayal2009 in the parameters the program has --
 p_11, the two rows of A_row and phi_k.
 """
-import ctypes as C
-
 import numpy as np
 
-from . import _abi
-from .api import HHMMError, PreparedRequest, load_library
+from . import _stats
+from .api import load_library
 
 MODELS = ("hmm", "hmm-multinom")
 FIT_MODELS = MODELS + ("hmm-multinom-semisup", "hhmm-tayal2009")  # score / m_step / baum_welch
@@ -46,25 +44,14 @@ def prepare(model, data, draws, pairing="grid", device=-1):
     """(PreparedRequest, EstepResult, {name: array}) with the shape checks."""
     if model not in MODELS:
         raise ValueError(f"the E-step covers {MODELS}, not {model!r}")
-    pr = PreparedRequest(model, data, draws, [], pairing, device)
-    if pairing == "zip" and pr.N != pr.S:
-        raise ValueError(f"zip pairing needs n_series ({pr.N}) == n_draws ({pr.S})")
-    L = int(data.get("L", 0))
-    need = ("p_1k", "A_ij", "phi_k") if model == "hmm-multinom" else ("p_1k", "A_ij", "mu_k", "sigma_k")
-    want = {"p_1k": (pr.S, pr.K), "A_ij": (pr.S, pr.K, pr.K), "phi_k": (pr.S, pr.K, L), "mu_k": (pr.S, pr.K),
-            "sigma_k": (pr.S, pr.K)}
-    for name in need:
-        if name not in draws:
-            raise ValueError(f"{model} needs the draw array {name}")
-        if np.shape(draws[name]) != want[name]:
-            raise ValueError(f"{name} must have shape {want[name]}, got {np.shape(draws[name])}")
-    res = _abi.EstepResult()
-    out = {}
-    for name, shape in stat_shapes(model, pr.P, pr.K, L).items():
-        out[name] = np.full(shape, np.nan, dtype=np.float64, order="F")
-        setattr(res, name, out[name].ctypes.data)
-    res.pair_status = pr.status.ctypes.data
-    return pr, res, out
+
+    def param_shapes(S, K, L):
+        if model == "hmm-multinom":
+            return {"p_1k": (S, K), "A_ij": (S, K, K), "phi_k": (S, K, L)}
+        return {"p_1k": (S, K), "A_ij": (S, K, K), "mu_k": (S, K), "sigma_k": (S, K)}
+
+    return _stats.request(model, data, draws, pairing, device, param_shapes,
+                          lambda P, K, L: stat_shapes(model, P, K, L))
 
 
 def estep(model, data, draws, pairing="grid", device=-1, lib=None, return_status=False):
@@ -74,14 +61,7 @@ def estep(model, data, draws, pairing="grid", device=-1, lib=None, return_status
     (P, K, L) for hmm-multinom or w_k, s1_k, s2_k (P, K) for hmm.  A pair whose
     log-likelihood is -inf or NaN has NaN statistics."""
     lib = lib or load_library()
-    pr, res, out = prepare(model, data, draws, pairing, device)
-    st = lib.hhmm_estep(C.byref(pr.req), C.byref(res))
-    if st < 0:
-        raise HHMMError(st, lib.hhmm_last_error().decode())
-    if return_status:
-        out["pair_status"] = pr.status
-        out["status"] = st
-    return out
+    return _stats.call(lib, "estep", *prepare(model, data, draws, pairing, device), return_status)
 
 
 def pair_draw(pairing, P, S, N):

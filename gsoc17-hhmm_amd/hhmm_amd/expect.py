@@ -11,9 +11,8 @@ the exact score of the model-block log-likelihood (hhmm_amd.score) and feed
 the EM point fit (hhmm_amd.baum_welch).  hmm-multinom has no mask: its
 statistics are estep()'s, bit for bit.
 """
-import ctypes as C
-
-from .api import HHMMError, load_library
+from . import _stats
+from .api import load_library
 from .gibbs import MODELS, _request  # noqa: F401
 
 
@@ -27,11 +26,4 @@ def expected_stats(model, data, draws, pairing="grid", device=-1, lib=None, retu
     exact zero.  A pair whose log-likelihood is -inf or NaN has NaN
     statistics."""
     lib = lib or load_library()
-    pr, res, out = _request(model, data, draws, pairing, device)
-    st = lib.hhmm_expected_stats(C.byref(pr.req), C.byref(res))
-    if st < 0:
-        raise HHMMError(st, lib.hhmm_last_error().decode())
-    if return_status:
-        out["pair_status"] = pr.status
-        out["status"] = st
-    return out
+    return _stats.call(lib, "expected_stats", *_request(model, data, draws, pairing, device), return_status)

@@ -17,12 +17,10 @@ hhmm-tayal2009.stan:51 and :62): a transition or an initial state is counted
 only where the program multiplies its probability in.  hmm-multinom,
 hmm-multinom-semisup and hhmm-tayal2009 at K <= 8.
 """
-import ctypes as C
-
 import numpy as np
 
-from . import _abi
-from .api import HHMMError, PreparedRequest, _f64, load_library
+from . import _stats
+from .api import load_library
 
 MODELS = ("hmm-multinom", "hmm-multinom-semisup", "hhmm-tayal2009")
 
@@ -43,33 +41,14 @@ def _request(model, data, draws, pairing, device):
     """(PreparedRequest, EstepResult, {name: array}) with the shape checks; no uniforms yet."""
     if model not in MODELS:
         raise ValueError(f"the draw statistics cover {MODELS}, not {model!r}")
-    pr = PreparedRequest(model, data, draws, [], pairing, device)
-    if pairing == "zip" and pr.N != pr.S:
-        raise ValueError(f"zip pairing needs n_series ({pr.N}) == n_draws ({pr.S})")
-    L = int(data.get("L", 0))
-    for name, shape in param_shapes(model, pr.S, pr.K, L).items():
-        if name not in draws:
-            raise ValueError(f"{model} needs the draw array {name}")
-        if np.shape(draws[name]) != shape:
-            raise ValueError(f"{name} must have shape {shape}, got {np.shape(draws[name])}")
-    res = _abi.EstepResult()
-    out = {}
-    for name, shape in stat_shapes(pr.P, pr.K, L).items():
-        out[name] = np.full(shape, np.nan, dtype=np.float64, order="F")
-        setattr(res, name, out[name].ctypes.data)
-    res.pair_status = pr.status.ctypes.data
-    return pr, res, out
+    return _stats.request(model, data, draws, pairing, device, lambda S, K, L: param_shapes(model, S, K, L),
+                          stat_shapes)
 
 
 def prepare(model, data, draws, uniforms, pairing="grid", device=-1):
     """_request() plus the uniforms of the draw, shape (P, T_max)."""
     pr, res, out = _request(model, data, draws, pairing, device)
-    if uniforms is None:
-        raise ValueError("the draw needs uniforms of shape (P, T_max)")
-    uu = _f64(uniforms)
-    if uu.shape != (pr.P, pr.Tmax):
-        raise ValueError(f"uniforms must have shape {(pr.P, pr.Tmax)}, got {uu.shape}")
-    pr.req.ffbs_u = pr._ptr(uu)
+    _stats.add_uniforms(pr, uniforms)
     return pr, res, out
 
 
@@ -82,14 +61,7 @@ def draw_stats(model, data, draws, uniforms, pairing="grid", device=-1, lib=None
     whose log-likelihood is not finite, or whose draw is undefined at some step,
     has NaN statistics."""
     lib = lib or load_library()
-    pr, res, out = prepare(model, data, draws, uniforms, pairing, device)
-    st = lib.hhmm_draw_stats(C.byref(pr.req), C.byref(res))
-    if st < 0:
-        raise HHMMError(st, lib.hhmm_last_error().decode())
-    if return_status:
-        out["pair_status"] = pr.status
-        out["status"] = st
-    return out
+    return _stats.call(lib, "draw_stats", *prepare(model, data, draws, uniforms, pairing, device), return_status)
 
 
 def _dirichlet(torch, conc, generator):
@@ -169,29 +141,13 @@ def gibbs(model, data, init, n_iter, burn=0, thin=1, prior=None, seed=0, pairing
     pr, res, _out = _request(model, data, init, pairing, -1)
     P, K, Tmax, L = pr.P, pr.K, pr.Tmax, int(data.get("L", 0))
     # the request's arrays on the device (the parameters: updated in place every sweep)
-    keep = {arr.ctypes.data: torch.from_numpy(np.asarray(arr).reshape(-1, order="F").copy()).to(dev)
-            for arr in pr.keep}
-    names = list(param_shapes(model, P, K, L))
-    pbuf = {name: keep[getattr(pr.req.draws, name)] for name in names}
-    for struct in (pr.req.data, pr.req.draws):
-        for name, ctype in struct._fields_:
-            v = getattr(struct, name)
-            if ctype is C.c_void_p and v and v in keep:
-                setattr(struct, name, keep[v].data_ptr())
     ubuf = torch.empty(P * Tmax, dtype=torch.float64, device=dev)
     pr.req.ffbs_u = ubuf.data_ptr()
-    sbuf = {name: torch.empty(int(np.prod(shape)), dtype=torch.float64, device=dev)
-            for name, shape in stat_shapes(P, K, L).items()}
-    for name, t in sbuf.items():
-        setattr(res, name, t.data_ptr())
-    status = torch.zeros(P, dtype=torch.int32, device=dev)
-    res.pair_status = status.data_ptr()
+    run = _stats.DeviceStats(lib, "draw_stats", pr, res, stat_shapes(P, K, L))
+    names = list(param_shapes(model, P, K, L))
+    pbuf, sbuf = run.arrays, run.out
     views = {"n_1k": sbuf["n_1k"].view(K, P).t(), "xi_ij": sbuf["xi_ij"].view(K, K, P).permute(2, 1, 0),
              "c_kl": sbuf["c_kl"].view(L, K, P).permute(2, 1, 0)}
-    wsb = C.c_size_t(0)
-    if lib.hhmm_draw_stats_workspace_size(C.byref(pr.req), C.byref(wsb)) < 0:
-        raise HHMMError(_abi.ERR_INVALID_ARGUMENT, lib.hhmm_last_error().decode())
-    ws = torch.empty(max(int(wsb.value), 256), dtype=torch.uint8, device=dev)
     gen = torch.Generator(device=dev)
     gen.manual_seed(int(seed))
     trace = torch.empty((n_iter, P), dtype=torch.float64, device=dev)
@@ -199,10 +155,7 @@ def gibbs(model, data, init, n_iter, burn=0, thin=1, prior=None, seed=0, pairing
     for it in range(n_iter):
         torch.rand(P * Tmax, dtype=torch.float64, device=dev, generator=gen, out=ubuf)
         ubuf.neg_().add_(1.0)
-        st = lib.hhmm_draw_stats_device(C.byref(pr.req), C.byref(res), ws.data_ptr(), ws.numel(),
-                                        torch.cuda.current_stream().cuda_stream)
-        if st < 0:
-            raise HHMMError(st, lib.hhmm_last_error().decode())
+        run.run()
         trace[it] = sbuf["loglik"]
         new = conditional_draw(model, views, prior, gen)
         for name in names:

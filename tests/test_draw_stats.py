@@ -370,7 +370,7 @@ def compare(got, want, ref_loglik, tag):
 
 def check(engine, model, data, draws, u, pairing="grid"):
     """Host and device entries against the reference counts of the engine's own z_ffbs (the bit-exact path)."""
-    from draw_stats_devrun import DeviceDrawStats
+    from stats_devrun import DeviceDrawStats
     ref = hhmm_amd.gqs(model, data, draws, pars=["z_ffbs", "loglik"], pairing=pairing, uniforms=u, lib=engine)
     want = dsr.counts_pairs(model, data, ref["z_ffbs"], ref["loglik"], pairing, draws["phi_k"].shape[0])
     host = hhmm_amd.draw_stats(model, data, draws, u, pairing, lib=engine, return_status=True)
@@ -538,7 +538,7 @@ def test_gpu_nan_draw_is_nan_for_its_pairs_only(engine, model):
 @pytest.mark.gpu
 @pytest.mark.parametrize("bad", [10, 0, INT32_MIN])
 def test_gpu_device_entry_flags_invalid_data(engine, bad):
-    from draw_stats_devrun import DeviceDrawStats
+    from stats_devrun import DeviceDrawStats
     N, S, L = 4, 20, 9
     data, draws = make("hmm-multinom-semisup", N, S, 15, 4, L, seed=19)
     u = synth.ffbs_uniforms(N * S, 15, seed=20)

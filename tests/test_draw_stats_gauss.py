@@ -406,7 +406,7 @@ def compare(got, want, ref_loglik, b1, b2, tag):
 
 def check(engine, data, draws, u, pairing="grid"):
     """Host and device entries against the reference statistics of the engine's own z_ffbs (the bit-exact path)."""
-    from draw_stats_gauss_devrun import DeviceDrawStatsGauss
+    from stats_devrun import DeviceDrawStatsGauss
     S = draws["mu_k"].shape[0]
     r = hhmm_amd.gqs("hmm", data, draws, pars=["z_ffbs", "loglik"], pairing=pairing, uniforms=u, lib=engine)
     want = ref.stats_pairs(data, r["z_ffbs"], r["loglik"], pairing, S)
@@ -512,7 +512,7 @@ def test_gpu_nan_parameter_and_nan_observation_are_nan_for_their_pairs_only(engi
 @pytest.mark.gpu
 @pytest.mark.parametrize("bad", [0, 16, -3])
 def test_gpu_device_entry_flags_only_the_pair_with_T_out_of_range(engine, bad):
-    from draw_stats_gauss_devrun import DeviceDrawStatsGauss
+    from stats_devrun import DeviceDrawStatsGauss
     N, S, T = 4, 20, 15
     data, draws = make(N, S, T, 4, seed=19)
     data["T"] = np.array([T, 9, T, 4], dtype=np.int32)

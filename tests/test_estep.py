@@ -331,7 +331,7 @@ def test_gpu_nan_draw_is_nan_for_its_pairs_only(engine, model, K, L):
 @pytest.mark.gpu
 @pytest.mark.parametrize("model,K,L,pairing,N,S", [("hmm-multinom", 4, 9, "grid", 5, 30), ("hmm", 5, 0, "block", 4, 72)])
 def test_gpu_device_entry_is_the_host_entry(engine, model, K, L, pairing, N, S):
-    from estep_devrun import DeviceEstep
+    from stats_devrun import DeviceEstep
     data, draws = make(model, N, S, 23, K, L, seed=17)
     data["T"] = np.array([23, 1, 9, 17, 8][:N], dtype=np.int32)
     host = hhmm_amd.estep(model, data, draws, pairing, lib=engine)
@@ -346,7 +346,7 @@ def test_gpu_device_entry_is_the_host_entry(engine, model, K, L, pairing, N, S):
 @pytest.mark.gpu
 @pytest.mark.parametrize("bad", [10, 0, INT32_MIN])
 def test_gpu_device_entry_flags_invalid_data(engine, bad):
-    from estep_devrun import DeviceEstep
+    from stats_devrun import DeviceEstep
     N, S, L = 4, 20, 9
     data, draws = make("hmm-multinom", N, S, 15, 4, L, seed=19)
     clean = DeviceEstep(engine, "hmm-multinom", data, draws)
@@ -364,7 +364,7 @@ def test_gpu_device_entry_flags_invalid_data(engine, bad):
 
 @pytest.mark.gpu
 def test_gpu_device_entry_flags_a_length_outside_the_data_block(engine):
-    from estep_devrun import DeviceEstep
+    from stats_devrun import DeviceEstep
     data, draws = make("hmm", 3, 4, 9, 3, seed=23)
     data["T"] = np.array([9, 10, 0], dtype=np.int32)
     dv = DeviceEstep(engine, "hmm", data, draws)

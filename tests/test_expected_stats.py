@@ -344,7 +344,7 @@ def test_tayal_m_step_and_score_arithmetic():
 
 def check(engine, model, data, draws, pairing="grid"):
     """The host entry against the reference; the device entry bit-equal to the host entry."""
-    from expect_devrun import DeviceExpect
+    from stats_devrun import DeviceExpect
     got = hhmm_amd.expected_stats(model, data, draws, pairing, lib=engine, return_status=True)
     want = xr.expected_stats(model, data, draws, pairing)
     w = worst(got, want)
@@ -542,7 +542,7 @@ def test_gpu_nan_draw_is_nan_for_its_pairs_only(engine, model, name, idx):
 
 
 def _device(engine, model, data, draws):
-    from expect_devrun import DeviceExpect
+    from stats_devrun import DeviceExpect
     dv = DeviceExpect(engine, model, data, draws)
     assert dv.run() == 0
     return dv.stats()

@@ -1,0 +1,162 @@
+"""CPU: the four "statistics per (series, draw) pair" entries -- hhmm_estep,
+hhmm_draw_stats, hhmm_draw_stats_gauss, hhmm_expected_stats -- share one host
+path (csrc/hhmm_api.cpp stats_*, csrc/hhmm_stats.h), so the same fault gets
+the same answer from each, their workspaces agree, and the request fields an
+entry does not read stay ignored.  Every check here is decided before a
+device is needed.
+"""
+import ctypes as C
+import sys
+
+import numpy as np
+import pytest
+
+import hhmm_amd  # noqa: F401
+from hhmm_amd import _abi
+
+_estep = sys.modules["hhmm_amd.estep"]
+_gibbs = sys.modules["hhmm_amd.gibbs"]
+_gg = sys.modules["hhmm_amd.gibbs_gauss"]
+
+N, S, T, K, L = 2, 3, 9, 4, 3  # K = 4: hhmm-tayal2009's only K
+P = N * S
+DISCRETE = ("hmm-multinom", "hmm-multinom-semisup", "hhmm-tayal2009")
+# entry -> (its name in messages, the models it accepts, does it read ffbs_u)
+ENTRIES = {
+    "estep": ("E-step", ("hmm", "hmm-multinom"), False),
+    "draw_stats": ("draw statistics", DISCRETE, True),
+    "draw_stats_gauss": ("Gaussian draw statistics", ("hmm",), True),
+    "expected_stats": ("expected statistics", DISCRETE, False),
+}
+CASES = [(entry, model) for entry, (_name, models, _u) in ENTRIES.items() for model in models]
+
+
+def make(model):
+    g = np.random.Generator(np.random.Philox(key=4100))
+    if model == "hmm":
+        data = {"K": K, "x": g.normal(size=(N, T))}
+        draws = {"p_1k": g.dirichlet(np.full(K, 2.0), size=S), "A_ij": g.dirichlet(np.full(K, 2.0), size=(S, K)),
+                 "mu_k": np.sort(g.normal(size=(S, K)), axis=1), "sigma_k": g.uniform(0.5, 1.5, size=(S, K))}
+        return data, draws
+    data = {"K": K, "L": L, "x": g.integers(1, L + 1, size=(N, T)).astype(np.int32)}
+    phi = g.dirichlet(np.full(L, 2.0), size=(S, K))
+    if model == "hhmm-tayal2009":
+        data["sign"] = g.integers(1, 3, size=(N, T)).astype(np.int32)
+        return data, {"p_11": g.uniform(0.2, 0.8, size=S), "A_row": g.dirichlet(np.full(2, 2.0), size=(S, 2)),
+                      "phi_k": phi}
+    if model == "hmm-multinom-semisup":
+        data["g"] = g.integers(1, 4, size=(N, T)).astype(np.int32)
+        data["G"] = 3
+    return data, {"p_1k": g.dirichlet(np.full(K, 2.0), size=S), "A_ij": g.dirichlet(np.full(K, 2.0), size=(S, K)),
+                  "phi_k": phi}
+
+
+def prepared(entry, model):
+    """(PreparedRequest, EstepResult) of a request the entry accepts."""
+    data, draws = make(model)
+    u = np.random.Generator(np.random.Philox(key=4101)).uniform(0.1, 1.0, size=(P, T))
+    if entry == "estep":
+        pr, res, _out = _estep.prepare(model, data, draws, "grid")
+    elif entry == "draw_stats":
+        pr, res, _out = _gibbs.prepare(model, data, draws, u, "grid")
+    elif entry == "draw_stats_gauss":
+        pr, res, _out = _gg.prepare(data, draws, u, "grid")
+    else:
+        pr, res, _out = _gibbs._request(model, data, draws, "grid", -1)
+    assert pr.P == P
+    return pr, res
+
+
+def call(engine, entry, path, req, res):
+    """Status and message of hhmm_<entry> ("host") or hhmm_<entry>_device with a NULL workspace of size 0."""
+    if path == "host":
+        st = getattr(engine, "hhmm_" + entry)(req, res)
+    else:
+        st = getattr(engine, f"hhmm_{entry}_device")(req, res, None, 0, None)
+    return st, engine.hhmm_last_error().decode()
+
+
+def _set(field, value):
+    def f(pr):
+        obj = pr.req
+        *path, name = field.split(".")
+        for p in path:
+            obj = getattr(obj, p)
+        setattr(obj, name, value)
+    return f
+
+
+# fault -> (change to the request, or which argument is NULL; the status; a word of the message)
+FAULTS = {
+    "null_request": ("req", _abi.ERR_INVALID_ARGUMENT, "request"),
+    "null_result": ("res", _abi.ERR_INVALID_ARGUMENT, "result"),
+    "abi_1": (_set("abi_version", 1), _abi.ERR_INVALID_ARGUMENT, "abi"),
+    "model_0": (_set("model", 0), _abi.ERR_INVALID_ARGUMENT, "model id 0"),
+    "model_10": (_set("model", 10), _abi.ERR_INVALID_ARGUMENT, "model id 10"),
+    "K_9": (_set("data.K", 9), _abi.ERR_UNSUPPORTED, "K = 9"),
+    "device_set": (_set("device", _abi.DEVICE_SET), _abi.ERR_UNSUPPORTED, "DEVICE_SET"),
+}
+
+
+@pytest.mark.parametrize("path", ["host", "device"])
+@pytest.mark.parametrize("fault", sorted(FAULTS))
+@pytest.mark.parametrize("entry,model", CASES)
+def test_same_rejection_for_the_same_fault(engine, entry, model, fault, path):
+    change, status, word = FAULTS[fault]
+    pr, res = prepared(entry, model)
+    req_arg, res_arg = C.byref(pr.req), C.byref(res)
+    if change == "req":
+        req_arg = None
+    elif change == "res":
+        res_arg = None
+    else:
+        change(pr)
+    st, msg = call(engine, entry, path, req_arg, res_arg)
+    assert st == status, (entry, model, fault, path, st, msg)
+    assert msg.startswith(ENTRIES[entry][0] + ":") and word in msg, (entry, model, fault, path, msg)
+
+
+@pytest.mark.parametrize("entry", sorted(ENTRIES))
+def test_workspace_size_rejects_null_arguments(engine, entry):
+    size = getattr(engine, f"hhmm_{entry}_workspace_size")
+    pr, _res = prepared(entry, ENTRIES[entry][1][0])
+    ws = C.c_size_t(0)
+    assert size(None, C.byref(ws)) == _abi.ERR_INVALID_ARGUMENT
+    assert size(C.byref(pr.req), None) == _abi.ERR_INVALID_ARGUMENT
+
+
+def fb_chunk(k):
+    return 8 if k <= 4 else 4
+
+
+@pytest.mark.parametrize("k", [4, 5])  # either side of fb_chunk's change from 8 to 4
+def test_workspace_sizes_agree(engine, k):
+    """ceil(T_max / fb_chunk(K)) * K * P * 8 bytes from all four, whatever the model."""
+    want = -(-T // fb_chunk(k)) * k * P * 8
+    for entry, model in CASES:
+        pr, _res = prepared(entry, model)
+        pr.req.data.K = k
+        ws = C.c_size_t(0)
+        st = getattr(engine, f"hhmm_{entry}_workspace_size")(C.byref(pr.req), C.byref(ws))
+        assert st == _abi.OK and ws.value == want, (entry, model, k, st, ws.value, want)
+
+
+@pytest.mark.parametrize("entry,model", CASES)
+def test_ignored_fields_stay_ignored(engine, entry, model):
+    """outputs = 0, hat_rand = NULL and (where the entry reads no uniforms) ffbs_u = NULL
+    pass the argument checks: without a GPU the answer is NO_DEVICE, with one the NULL
+    workspace is refused -- no kernel runs either way.  The two draw entries need ffbs_u."""
+    reads_u = ENTRIES[entry][2]
+    pr, res = prepared(entry, model)
+    pr.req.outputs = 0
+    pr.req.hat_rand = None
+    if not reads_u:
+        pr.req.ffbs_u = None
+    st, msg = call(engine, entry, "device", C.byref(pr.req), C.byref(res))
+    assert st == _abi.ERR_NO_DEVICE or (st == _abi.ERR_INVALID_ARGUMENT and "workspace" in msg), (entry, model, st, msg)
+    if reads_u:
+        pr.req.ffbs_u = None
+        for path in ("device", "host"):
+            st, msg = call(engine, entry, path, C.byref(pr.req), C.byref(res))
+            assert st == _abi.ERR_INVALID_ARGUMENT and "ffbs_u" in msg, (entry, model, path, st, msg)
+            assert msg.startswith(ENTRIES[entry][0] + ":"), msg
