@@ -5,9 +5,9 @@
  * block and parameter constraints would (declared bounds such as
  * `int<lower=1, upper=L> x[T]`, hmm/stan/hmm-multinom.stan:12), sizes the
  * workspace, moves host arrays to and from the device for the R path
- * (hhmm_run), and launches the gfx950 kernels (hhmm_kernels.hip).  There is
- * no CPU compute path: without a gfx950 device every entry point fails with
- * HHMM_ERR_NO_DEVICE.
+ * (hhmm_run; its plan and host staging are hhmm_stage.cpp), and launches the
+ * gfx950 kernels (hhmm_kernels.hip).  There is no CPU compute path: without a
+ * gfx950 device every entry point fails with HHMM_ERR_NO_DEVICE.
  */
 #include <hip/hip_runtime.h>
 
@@ -20,9 +20,9 @@
 #include <thread>
 #include <vector>
 #include <algorithm>
-#include <emmintrin.h>
 
 #include "hhmm_internal.h"
+#include "hhmm_stage.h"
 #include "build_id.h" /* HHMM_SOURCE_HASH (Makefile) */
 
 namespace hhmm {
@@ -268,32 +268,6 @@ static bool device_supported(int m)
     return m >= HHMM_MODEL_HMM_GAUSS && m <= HHMM_MODEL_TAYAL_LITE;
 }
 
-static int64_t npairs(const hhmm_request *r)
-{
-    if (!r)
-        return -1;
-    if (r->data.n_series < 1 || r->draws.n_draws < 1)
-        return -1;
-    if (r->pairing == HHMM_PAIR_ZIP)
-        return r->data.n_series == r->draws.n_draws ? r->data.n_series : -1;
-    if (r->pairing == HHMM_PAIR_GRID)
-        return r->data.n_series * r->draws.n_draws;
-    if (r->pairing == HHMM_PAIR_BLOCK)
-        return r->draws.n_draws % r->data.n_series == 0 ? r->draws.n_draws : -1;
-    return -1;
-}
-
-/* One array of the request: where it lives and how many elements. */
-enum ArrayClass { SERIES = 0, DRAWS = 1, PAIRS = 2 }; /* leading (fastest) dimension N, S or P */
-struct ArrayDesc {
-    const void *host;
-    void **dev_slot; /* field in the device copy of the request/result */
-    size_t elems;
-    size_t esize;
-    bool output;
-    int cls;         /* ArrayClass */
-};
-
 #define REQUIRE(cond, ...)                                                                          \
     do {                                                                                            \
         if (!(cond)) {                                                                              \
@@ -333,20 +307,9 @@ static bool any_out_of_range(const int32_t *v, int64_t N, int Tm, const int32_t 
     if (nt <= 1)
         return rows(0, Tm);
     std::vector<char> res((size_t)nt, 0);
-    auto part = [&](int i) { res[(size_t)i] = rows((int)((int64_t)Tm * i / nt), (int)((int64_t)Tm * (i + 1) / nt)); };
-    std::vector<std::thread> th;
-    std::vector<int> mine{0};
-    for (int i = 1; i < nt; ++i) {
-        try {
-            th.emplace_back(part, i);
-        } catch (...) { /* no exception crosses the C ABI: this thread takes the share */
-            mine.push_back(i);
-        }
-    }
-    for (int i : mine)
-        part(i);
-    for (auto &x : th)
-        x.join();
+    run_parallel((size_t)nt, [&](size_t i) {
+        res[i] = rows((int)((int64_t)Tm * (int64_t)i / nt), (int)((int64_t)Tm * (int64_t)(i + 1) / nt));
+    });
     for (char c : res)
         if (c)
             return true;
@@ -488,76 +451,6 @@ static hhmm_status validate(const hhmm_request *r, const hhmm_result *o, bool ho
     return validate_impl(r, o, host);
 }
 
-/* Element counts of every input / output array the request uses. */
-static void describe(const hhmm_request *r, const hhmm_result *o, hhmm_request *dr, hhmm_result *dq,
-                     std::vector<ArrayDesc> &v)
-{
-    const hhmm_data &d = r->data;
-    const hhmm_draws &w = r->draws;
-    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max;
-    const size_t To = (size_t)(d.T_oos_max > 0 ? d.T_oos_max : 0);
-    const size_t K = (size_t)d.K, L = (size_t)(d.L > 0 ? d.L : 0), M = (size_t)(d.M > 0 ? d.M : 0);
-    const size_t P = (size_t)npairs(r);
-    const uint32_t out = r->outputs;
-    /* the class follows from the leading dimension of the element count */
-    auto cls_of = [&](size_t lead) { return lead == 0 ? (int)SERIES : lead == 1 ? (int)DRAWS : (int)PAIRS; };
-    auto in = [&](const void *h, const void **slot, size_t n, size_t es, int lead) {
-        if (h)
-            v.push_back({h, (void **)slot, n, es, false, cls_of((size_t)lead)});
-    };
-    auto ou = [&](uint32_t bit, void *h, void **slot, size_t n, size_t es) {
-        if ((out & bit) && h)
-            v.push_back({h, slot, n, es, true, PAIRS});
-        else
-            *slot = nullptr;
-    };
-    in(d.T, (const void **)&dr->data.T, N, 4, 0);
-    in(d.x_int, (const void **)&dr->data.x_int, N * Tm, 4, 0);
-    in(d.x_real, (const void **)&dr->data.x_real, N * Tm, 8, 0);
-    in(d.g, (const void **)&dr->data.g, N * Tm, 4, 0);
-    in(d.sign, (const void **)&dr->data.sign, N * Tm, 4, 0);
-    in(d.u, (const void **)&dr->data.u, N * Tm * M, 8, 0);
-    in(d.T_oos, (const void **)&dr->data.T_oos, N, 4, 0);
-    in(d.x_oos, (const void **)&dr->data.x_oos, N * To, 4, 0);
-    in(d.sign_oos, (const void **)&dr->data.sign_oos, N * To, 4, 0);
-    dr->data.hyperparams = nullptr;
-    in(w.p_1k, (const void **)&dr->draws.p_1k, S * K, 8, 1);
-    in(w.A_ij, (const void **)&dr->draws.A_ij, S * K * K, 8, 1);
-    in(w.phi_k, (const void **)&dr->draws.phi_k, S * K * L, 8, 1);
-    in(w.mu_k, (const void **)&dr->draws.mu_k, S * K, 8, 1);
-    in(w.sigma_k, (const void **)&dr->draws.sigma_k, S * K, 8, 1);
-    in(w.w_km, (const void **)&dr->draws.w_km, S * K * M, 8, 1);
-    in(w.b_km, (const void **)&dr->draws.b_km, S * K * M, 8, 1);
-    in(w.s_k, (const void **)&dr->draws.s_k, S * K, 8, 1);
-    in(w.lambda_kl, (const void **)&dr->draws.lambda_kl, S * K * L, 8, 1);
-    in(w.mu_kl, (const void **)&dr->draws.mu_kl, S * K * L, 8, 1);
-    in(w.s_kl, (const void **)&dr->draws.s_kl, S * K * L, 8, 1);
-    in(w.p_11, (const void **)&dr->draws.p_11, S, 8, 1);
-    in(w.A_row, (const void **)&dr->draws.A_row, S * 4, 8, 1);
-    in(r->ffbs_u, (const void **)&dr->ffbs_u, P * Tm, 8, 2);
-    in(r->hat_rand, (const void **)&dr->hat_rand, P * Tm * 3, 8, 2);
-    const size_t Tz = (r->model == HHMM_MODEL_TAYAL_LITE) ? To : Tm;
-    ou(HHMM_OUT_LOGLIK, o->loglik, (void **)&dq->loglik, P, 8);
-    ou(HHMM_OUT_UNALPHA, o->unalpha_tk, (void **)&dq->unalpha_tk, P * Tm * K, 8);
-    ou(HHMM_OUT_ALPHA, o->alpha_tk, (void **)&dq->alpha_tk, P * Tm * K, 8);
-    ou(HHMM_OUT_UNBETA, o->unbeta_tk, (void **)&dq->unbeta_tk, P * Tm * K, 8);
-    ou(HHMM_OUT_BETA, o->beta_tk, (void **)&dq->beta_tk, P * Tm * K, 8);
-    ou(HHMM_OUT_UNGAMMA, o->ungamma_tk, (void **)&dq->ungamma_tk, P * Tm * K, 8);
-    ou(HHMM_OUT_GAMMA, o->gamma_tk, (void **)&dq->gamma_tk, P * Tm * K, 8);
-    ou(HHMM_OUT_ZSTAR, o->zstar_t, (void **)&dq->zstar_t, P * Tz, 4);
-    ou(HHMM_OUT_LOGP_ZSTAR, o->logp_zstar, (void **)&dq->logp_zstar, P, 8);
-    ou(HHMM_OUT_OBLIK_TK, o->oblik_tk, (void **)&dq->oblik_tk, P * Tm * K, 8);
-    ou(HHMM_OUT_OBLIK_T, o->oblik_t, (void **)&dq->oblik_t, P * Tm, 8);
-    ou(HHMM_OUT_FFBS, o->z_ffbs, (void **)&dq->z_ffbs, P * Tm, 4);
-    ou(HHMM_OUT_ALPHA_OOS, o->alpha_tk_oos, (void **)&dq->alpha_tk_oos, P * To * K, 8);
-    ou(HHMM_OUT_UNALPHA_OOS, o->unalpha_tk_oos, (void **)&dq->unalpha_tk_oos, P * To * K, 8);
-    ou(HHMM_OUT_LOGA, o->logA_ij, (void **)&dq->logA_ij, P * Tm * K, 8);
-    ou(HHMM_OUT_HATPI, o->hatpi_tk, (void **)&dq->hatpi_tk, P * Tm * K, 8);
-    ou(HHMM_OUT_HATZ, o->hatz_t, (void **)&dq->hatz_t, P * Tm, 4);
-    ou(HHMM_OUT_HATL, o->hatl_t, (void **)&dq->hatl_t, P * Tm, 4);
-    ou(HHMM_OUT_HATX, o->hatx_t, (void **)&dq->hatx_t, P * Tm, 8);
-}
-
 static hhmm_status hip_fail(hipError_t e, const char *what)
 {
     set_error("%s: %s", what, hipGetErrorString(e));
@@ -597,75 +490,10 @@ static DevSet &devset()
     static DevSet d;
     return d;
 }
-
-/* One shard of a host request: per array class (series, draws, pairs) the
- * first element, the element count and the caller's leading extent.  An
- * array of class c with e elements is then `e / lead` rows of `cnt` elements,
- * at a pitch of `lead` in the caller's buffer and packed in the shard's
- * device copy -- which is exactly the [N', ...] / [S', ...] / [P', ...]
- * layout of the sub-request (every array is series-, draw- or pair-fastest). */
-struct Shard {
-    int64_t off[3], cnt[3], lead[3];
-};
-
-static Shard whole_shard(const hhmm_request *r)
+static std::vector<int> device_set()
 {
-    const int64_t N = r->data.n_series, S = r->draws.n_draws, P = npairs(r);
-    return Shard{{0, 0, 0}, {N, S, P}, {N, S, P}};
-}
-
-/* Splits a request over `n` shards: contiguous series ranges (ZIP / BLOCK take
- * the series' own draws, GRID all draws); a GRID request with fewer series
- * than shards splits its draws instead (pairs p = s + S*n with s in the
- * range: rows of S' pairs at a pitch of S). */
-static std::vector<Shard> make_shards(const hhmm_request *r, int n)
-{
-    const int64_t N = r->data.n_series, S = r->draws.n_draws, P = npairs(r);
-    std::vector<Shard> v;
-    const bool by_draws = r->pairing == HHMM_PAIR_GRID && N < n;
-    const int64_t units = by_draws ? S : N;
-    const int64_t ns = std::min<int64_t>(n, units);
-    for (int64_t i = 0; i < ns; ++i) {
-        const int64_t a = units * i / ns, b = units * (i + 1) / ns;
-        Shard sh;
-        if (by_draws) {
-            sh = Shard{{0, a, a}, {N, b - a, b - a}, {N, S, S}};
-        } else if (r->pairing == HHMM_PAIR_ZIP) {
-            sh = Shard{{a, a, a}, {b - a, b - a, b - a}, {N, S, P}};
-        } else if (r->pairing == HHMM_PAIR_BLOCK) {
-            const int64_t B = S / N;
-            sh = Shard{{a, B * a, B * a}, {b - a, B * (b - a), B * (b - a)}, {N, S, P}};
-        } else { /* GRID by series */
-            sh = Shard{{a, 0, S * a}, {b - a, S, S * (b - a)}, {N, S, P}};
-        }
-        v.push_back(sh);
-    }
-    return v;
-}
-
-/* One array's shard in the caller's buffer: `rows` rows of `width` bytes at a
- * pitch of `pitch` bytes from `base`; packed (pitch = width) in the shard's copy. */
-struct ShardRows {
-    char *base;
-    size_t rows, width, pitch;
-};
-static ShardRows shard_rows(const void *host, const ArrayDesc &a, const Shard &sh)
-{
-    const size_t es = a.esize, lead = (size_t)sh.lead[a.cls], cnt = (size_t)sh.cnt[a.cls];
-    return ShardRows{(char *)host + (size_t)sh.off[a.cls] * es, a.elems / lead, cnt * es, lead * es};
-}
-
-/* A shard's rows packed / unpacked on the host for hhmm_selftest_shards (memcpy per row). */
-static void copy_shard_host(void *packed, const void *host, const ArrayDesc &a, const Shard &sh, bool to_packed)
-{
-    const ShardRows r = shard_rows(host, a, sh);
-    for (size_t i = 0; i < r.rows; ++i) {
-        char *h = r.base + i * r.pitch, *q = (char *)packed + i * r.width;
-        if (to_packed)
-            memcpy(q, h, r.width);
-        else
-            memcpy(h, q, r.width);
-    }
+    std::lock_guard<std::mutex> g(devset().mu);
+    return devset().devs.empty() ? std::vector<int>{0} : devset().devs;
 }
 
 /* ---------------- the R path: a pipelined host request ----------------
@@ -764,196 +592,23 @@ static hhmm_status get_pipe_streams(int dev, hipStream_t (&st)[3])
     return HHMM_OK;
 }
 
-/* One row of a staging copy.  Large rows leave the cache alone: the
- * destination is written with streaming stores (no read-for-ownership of the
- * caller's lines, which would double the DRAM traffic of the scatter into R's
- * arrays), 16 bytes at a time once it is 16-byte aligned. */
-static void copy_row(char *dst, const char *src, size_t n)
+/* The whole request runs no parallel scan over T.  Only then may it be cut
+ * into chunks or ranges: with kSequentialFlags pinned they take the same
+ * sequential recursions, and the outputs are bit-identical to one device call. */
+static bool runs_sequentially(const hhmm_request *req)
 {
-    if (n < 4096) {
-        memcpy(dst, src, n);
-        return;
-    }
-    const size_t head = (16 - ((uintptr_t)dst & 15)) & 15;
-    memcpy(dst, src, head);
-    dst += head;
-    src += head;
-    n -= head;
-    const size_t m = n & ~(size_t)63;
-    for (size_t i = 0; i < m; i += 64) {
-        const __m128i a = _mm_loadu_si128((const __m128i *)(src + i));
-        const __m128i b = _mm_loadu_si128((const __m128i *)(src + i + 16));
-        const __m128i c = _mm_loadu_si128((const __m128i *)(src + i + 32));
-        const __m128i d = _mm_loadu_si128((const __m128i *)(src + i + 48));
-        _mm_stream_si128((__m128i *)(dst + i), a);
-        _mm_stream_si128((__m128i *)(dst + i + 16), b);
-        _mm_stream_si128((__m128i *)(dst + i + 32), c);
-        _mm_stream_si128((__m128i *)(dst + i + 48), d);
-    }
-    memcpy(dst + m, src + m, n - m);
+    const hhmm_data &d = req->data;
+    const int64_t Pw = npairs(req);
+    return scan_plan(req->model, d.K, d.T_max, Pw, req->outputs, (uint32_t)req->flags).cl == 0 &&
+           vscan_chunks(req->model, d.K, req->model == HHMM_MODEL_TAYAL_LITE ? d.T_oos_max : d.T_max, Pw, req->outputs,
+                        (uint32_t)req->flags) == 0;
 }
-
-/* rows x width bytes between pitched buffers, split over host threads when
- * the copy is large (the staging copies run beside the GPU's DMA; up to 16
- * threads, the CPU share of one GPU on an 8-GPU node) */
-static void par_copy_rows(char *dst, size_t dpitch, const char *src, size_t spitch, size_t width, size_t rows)
-{
-    if (rows == 0 || width == 0)
-        return;
-    if (dpitch == width && spitch == width) { /* contiguous: one long row, split in pieces */
-        width *= rows;
-        rows = 1;
-        dpitch = spitch = width;
-    }
-    const size_t total = width * rows;
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const size_t nt = total < ((size_t)4 << 20) ? 1 : std::min<size_t>(16u, hw);
-    /* work item i: a range of rows, or of bytes of the single row */
-    auto run = [&](size_t i) {
-        if (rows >= nt) {
-            const size_t r0 = rows * i / nt, r1 = rows * (i + 1) / nt;
-            for (size_t r = r0; r < r1; ++r)
-                copy_row(dst + r * dpitch, src + r * spitch, width);
-        } else {
-            for (size_t r = 0; r < rows; ++r) {
-                const size_t b0 = (width * i / nt) & ~(size_t)63, b1 = i + 1 == nt ? width : (width * (i + 1) / nt) & ~(size_t)63;
-                copy_row(dst + r * dpitch + b0, src + r * spitch + b0, b1 - b0);
-            }
-        }
-        _mm_sfence(); /* this thread's streaming stores, before the join */
-    };
-    if (nt <= 1) {
-        run(0);
-        return;
-    }
-    /* a thread that cannot be started leaves its share to this one (no
-     * exception crosses the C ABI) */
-    std::vector<std::thread> th;
-    std::vector<size_t> mine{0};
-    for (size_t i = 1; i < nt; ++i) {
-        try {
-            th.emplace_back(run, i);
-        } catch (...) {
-            mine.push_back(i);
-        }
-    }
-    for (size_t i : mine)
-        run(i);
-    for (auto &t : th)
-        t.join();
-}
-
-/* A chunk: its shard, its sub-request, and where each array sits in the slot. */
-struct ChunkLayout {
-    Shard sh;
-    std::vector<size_t> off;   /* per array of `arrays`, bytes from the slot base */
-    size_t status_off = 0;
-    size_t in_end = 0;         /* [0, in_end): uploaded */
-    size_t out_begin = 0;      /* [out_begin, total): downloaded */
-    size_t total = 0;
-    int64_t P = 0;
-};
-
-static size_t shard_bytes(const ArrayDesc &a, const Shard &sh)
-{
-    return a.elems / (size_t)sh.lead[a.cls] * (size_t)sh.cnt[a.cls] * a.esize;
-}
-
-static ChunkLayout chunk_layout(const hhmm_request *req, const std::vector<ArrayDesc> &arrays, const Shard &sh,
-                                bool ragged)
-{
-    ChunkLayout L;
-    L.sh = sh;
-    hhmm_request r = *req;
-    r.data.n_series = sh.cnt[SERIES];
-    r.draws.n_draws = sh.cnt[DRAWS];
-    L.P = npairs(&r);
-    L.off.assign(arrays.size(), 0);
-    size_t o = 0;
-    auto place = [&](size_t bytes) {
-        const size_t at = o;
-        o += (bytes + 255) & ~(size_t)255;
-        return at;
-    };
-    for (size_t i = 0; i < arrays.size(); ++i) /* inputs first */
-        if (!arrays[i].output)
-            L.off[i] = place(shard_bytes(arrays[i], sh));
-    const size_t outs = o;
-    for (size_t i = 0; i < arrays.size(); ++i)
-        if (arrays[i].output)
-            L.off[i] = place(shard_bytes(arrays[i], sh));
-    L.status_off = place((size_t)L.P * sizeof(int32_t));
-    L.total = o;
-    /* outputs travel up too where padded steps must round-trip untouched */
-    L.in_end = ragged ? L.status_off : outs;
-    L.out_begin = outs;
-    return L;
-}
-
-/* The pairs a chunk's PAIRS-class slices hold (rows of cnt at a pitch of lead)
- * must be the pairs its sub-request computes: the kernels write L.P pairs of
- * every output into slots sized from the slices, so a planner mistake here
- * would be a device overrun. */
-static int64_t chunk_staged_pairs(const hhmm_request *req, const Shard &c)
-{
-    return c.lead[PAIRS] > 0 ? c.cnt[PAIRS] * (npairs(req) / c.lead[PAIRS]) : -1;
-}
-static bool chunk_pairs_agree(const hhmm_request *req, const Shard &c, const ChunkLayout &L)
-{
-    return chunk_staged_pairs(req, c) == L.P;
-}
-
-/* Sub-shards of a device shard: `n` contiguous ranges of its units (series,
- * or draws for a GRID request split by draws), each a Shard of the request. */
-static std::vector<Shard> split_shard(const hhmm_request *r, const Shard &sh, int64_t n)
-{
-    const int64_t S = r->draws.n_draws;
-    if (n <= 1)
-        return {sh};
-    /* a GRID shard holding every series splits by draws (rows of the chunk's
-     * draws at a pitch of S pairs) when it is a draws shard already or has
-     * fewer series than chunks; every other shard splits by series.  A draws
-     * shard is known by its layout (its pairs lie at a pitch of S, not packed
-     * over the request's P), not by holding fewer than S draws: at S = 1 it
-     * holds them all.  With one series the two layouts coincide and the shard
-     * splits by draws through `cnt[SERIES] < n`. */
-    const bool all_series = sh.cnt[SERIES] == r->data.n_series;
-    const bool draws_shard = sh.lead[PAIRS] != npairs(r);
-    const bool by_draws = r->pairing == HHMM_PAIR_GRID && all_series && (draws_shard || sh.cnt[SERIES] < n);
-    const int64_t u0 = by_draws ? sh.off[DRAWS] : sh.off[SERIES];
-    const int64_t units = by_draws ? sh.cnt[DRAWS] : sh.cnt[SERIES];
-    const int64_t ns = std::max<int64_t>(1, std::min(n, units));
-    std::vector<Shard> v;
-    for (int64_t i = 0; i < ns; ++i) {
-        const int64_t a = u0 + units * i / ns, b = u0 + units * (i + 1) / ns;
-        Shard c = sh;
-        if (by_draws) {
-            c.lead[PAIRS] = S;
-            c.off[DRAWS] = c.off[PAIRS] = a;
-            c.cnt[DRAWS] = c.cnt[PAIRS] = b - a;
-        } else {
-            const int64_t per = sh.cnt[SERIES] > 0 ? sh.cnt[PAIRS] / sh.cnt[SERIES] : 0; /* pairs per series */
-            const int64_t dper = sh.cnt[SERIES] > 0 ? sh.cnt[DRAWS] / sh.cnt[SERIES] : 0;
-            c.off[SERIES] = a;
-            c.cnt[SERIES] = b - a;
-            c.off[PAIRS] = sh.off[PAIRS] + (a - u0) * per;
-            c.cnt[PAIRS] = (b - a) * per;
-            if (r->pairing != HHMM_PAIR_GRID) { /* ZIP / BLOCK: the series' own draws */
-                c.off[DRAWS] = sh.off[DRAWS] + (a - u0) * dper;
-                c.cnt[DRAWS] = (b - a) * dper;
-            }
-        }
-        v.push_back(c);
-    }
-    return v;
-}
+constexpr int32_t kSequentialFlags = (int32_t)(HHMM_FLAG_SCAN_OFF | HHMM_FLAG_VIT_SCAN_OFF);
 
 /* Chunks of a device shard: about kChunkBytes of staged traffic each, with at
  * least kChunkMinPairs pairs (256 waves) so a chunk's kernels still fill the
- * chip, and only where the whole request runs no parallel scan over T: the
- * chunks then take the same sequential recursions (SCAN_OFF / VIT_SCAN_OFF
- * pin it) and the outputs are bit-identical to one device call.
- * HHMM_FLAG_HOST_CHUNKS(n) asks for n chunks. */
+ * chip, and only where the request runs_sequentially (pin_flags: the caller
+ * pins kSequentialFlags).  HHMM_FLAG_HOST_CHUNKS(n) asks for n chunks. */
 constexpr size_t kChunkBytes = (size_t)512 << 20;
 constexpr int64_t kChunkMinPairs = 16384;
 
@@ -961,12 +616,7 @@ static int64_t choose_chunks(const hhmm_request *req, const std::vector<ArrayDes
                              bool ragged, bool &pin_flags)
 {
     pin_flags = false;
-    const hhmm_data &d = req->data;
-    const int64_t Pw = npairs(req);
-    const bool seq = scan_plan(req->model, d.K, d.T_max, Pw, req->outputs, (uint32_t)req->flags).cl == 0 &&
-                     vscan_chunks(req->model, d.K, req->model == HHMM_MODEL_TAYAL_LITE ? d.T_oos_max : d.T_max, Pw,
-                                  req->outputs, (uint32_t)req->flags) == 0;
-    if (!seq)
+    if (!runs_sequentially(req))
         return 1;
     const int64_t forced = (int64_t)(((uint32_t)req->flags >> 20) & 0xffu);
     size_t bytes = 0; /* staged bytes of the shard, both directions */
@@ -979,6 +629,25 @@ static int64_t choose_chunks(const hhmm_request *req, const std::vector<ArrayDes
     n = std::max<int64_t>(1, n);
     pin_flags = n > 1;
     return n;
+}
+
+/* The tail of a device path whose launch (ls) or HIP call (e) failed.  A
+ * failed launch may follow one that is still running: drain() waits for the
+ * request's streams before cleanup() hands its pooled buffers to another
+ * request; a sticky device error from an earlier fault is reported beside the
+ * launch error instead of being buried under it. */
+template <class Drain, class Cleanup>
+static hhmm_status fail_drained(hhmm_status ls, hipError_t e, Drain drain, Cleanup cleanup, const char *what,
+                                const char *streams)
+{
+    const std::string first = hhmm_last_error();
+    const hipError_t d = drain();
+    cleanup();
+    if (ls == HHMM_OK)
+        return hip_fail(e, what);
+    if (d != hipSuccess)
+        set_error("%s; draining the request's %s then failed: %s", first.c_str(), streams, hipGetErrorString(d));
+    return ls;
 }
 
 /* Runs one shard of a host request on the current device (the pipeline
@@ -1022,7 +691,7 @@ static hhmm_status run_on_device(const hhmm_request *req, hhmm_result *res, cons
                                             c.cnt[SERIES], dreq.pairing));
     }
     if (pin)
-        dreq.flags |= (int32_t)(HHMM_FLAG_SCAN_OFF | HHMM_FLAG_VIT_SCAN_OFF);
+        dreq.flags |= kSequentialFlags;
     const int nslot = chunks.size() > 1 ? 2 : 1;
     hipStream_t st[3];
     hhmm_status s = get_pipe_streams(dev, st);
@@ -1072,53 +741,8 @@ static hhmm_status run_on_device(const hhmm_request *req, hhmm_result *res, cons
         return HHMM_ERR_OUT_OF_MEMORY;
     }
 
-    auto bind = [&](const ChunkLayout &L, int k, hhmm_request &cr, hhmm_result &cq) {
-        cr = dreq;
-        cq = dres;
-        cr.data.n_series = L.sh.cnt[SERIES];
-        cr.draws.n_draws = L.sh.cnt[DRAWS];
-        /* the device copies of the request's arrays: describe() recorded where
-         * each pointer lives in dreq / dres; the same field of cr / cq */
-        for (size_t i = 0; i < arrays.size(); ++i) {
-            const char *slot_base = (const char *)arrays[i].dev_slot;
-            void **f = nullptr;
-            if (slot_base >= (const char *)&dreq && slot_base < (const char *)(&dreq + 1))
-                f = (void **)((char *)&cr + (slot_base - (const char *)&dreq));
-            else
-                f = (void **)((char *)&cq + (slot_base - (const char *)&dres));
-            *f = (char *)dslot[k] + L.off[i];
-        }
-        cq.pair_status = (int32_t *)((char *)dslot[k] + L.status_off);
-    };
-    auto gather = [&](const ChunkLayout &L, int k) {
-        for (size_t i = 0; i < arrays.size(); ++i) {
-            const ArrayDesc &a = arrays[i];
-            if (L.off[i] >= L.in_end)
-                continue;
-            const ShardRows r = shard_rows(a.host, a, L.sh);
-            par_copy_rows((char *)hin[k] + L.off[i], r.width, r.base, r.pitch, r.width, r.rows);
-        }
-    };
+    const int64_t Pw = npairs(req);
     int64_t fails = 0;
-    auto scatter = [&](const ChunkLayout &L, int k) {
-        for (size_t i = 0; i < arrays.size(); ++i) {
-            const ArrayDesc &a = arrays[i];
-            if (!a.output)
-                continue;
-            const ShardRows r = shard_rows(a.host, a, L.sh);
-            par_copy_rows(r.base, r.pitch, (const char *)hout[k] + (L.off[i] - L.out_begin), r.width, r.width,
-                          r.rows);
-        }
-        /* pair_status: [P] in the caller's layout (a PAIRS array of P elements) */
-        const ArrayDesc sa{status, nullptr, (size_t)npairs(req), sizeof(int32_t), true, PAIRS};
-        const ShardRows r = shard_rows(status, sa, L.sh);
-        const char *src = (const char *)hout[k] + (L.status_off - L.out_begin);
-        par_copy_rows(r.base, r.pitch, src, r.width, r.width, r.rows);
-        const int32_t *q = (const int32_t *)src;
-        for (int64_t p = 0; p < L.P; ++p)
-            fails += q[p] != 0;
-    };
-
     hhmm_status ls = HHMM_OK;
     const size_t n = chunks.size();
     for (size_t i = 0; i < n && ls == HHMM_OK; ++i) {
@@ -1126,7 +750,7 @@ static hhmm_status run_on_device(const hhmm_request *req, hhmm_result *res, cons
         const ChunkLayout &L = lay[i];
         if (i >= (size_t)nslot && (e = hipEventSynchronize(ev[0][k])) != hipSuccess) /* pinned in-slot free */
             break;
-        gather(L, k);
+        gather_chunk(arrays, L, hin[k]);
         if (i >= (size_t)nslot && (e = hipStreamWaitEvent(st[0], ev[2][k], 0)) != hipSuccess) /* device slot free */
             break;
         if ((e = hipMemcpyAsync(dslot[k], hin[k], L.in_end, hipMemcpyHostToDevice, st[0])) != hipSuccess ||
@@ -1137,7 +761,7 @@ static hhmm_status run_on_device(const hhmm_request *req, hhmm_result *res, cons
             break;
         hhmm_request cr;
         hhmm_result cq;
-        bind(L, k, cr, cq);
+        bind_chunk(arrays, L, dslot[k], dreq, dres, cr, cq);
         ls = launch_all(&cr, &cq, L.P, ws, st[1]);
         if (ls != HHMM_OK)
             break;
@@ -1151,31 +775,63 @@ static hhmm_status run_on_device(const hhmm_request *req, hhmm_result *res, cons
             const int kp = (int)((i - 1) % (size_t)nslot);
             if ((e = hipEventSynchronize(ev[2][kp])) != hipSuccess)
                 break;
-            scatter(lay[i - 1], kp);
+            fails += scatter_chunk(arrays, lay[i - 1], hout[kp], status, Pw);
         }
     }
-    if (ls != HHMM_OK || e != hipSuccess) {
-        /* a failed launch may follow one that is still running: drain this
-         * request's streams before its pooled buffers can be handed to another
-         * request; a sticky device error from an earlier fault is reported
-         * beside the launch error instead of being buried under it */
-        const std::string first = hhmm_last_error();
-        const hipError_t d = drain();
-        cleanup();
-        if (ls == HHMM_OK)
-            return hip_fail(e, "host pipeline (copy or kernel execution)");
-        if (d != hipSuccess)
-            set_error("%s; draining the request's streams then failed: %s", first.c_str(), hipGetErrorString(d));
-        return ls;
-    }
+    if (ls != HHMM_OK || e != hipSuccess)
+        return fail_drained(ls, e, drain, cleanup, "host pipeline (copy or kernel execution)", "streams");
     e = drain();
     if (e != hipSuccess) {
         cleanup();
         return hip_fail(e, "kernel execution");
     }
-    scatter(lay[n - 1], (int)((n - 1) % (size_t)nslot));
+    fails += scatter_chunk(arrays, lay[n - 1], hout[(n - 1) % (size_t)nslot], status, Pw);
     cleanup();
     *failures = fails;
+    return HHMM_OK;
+}
+
+/* Item i of n on device devs[i], each on a host thread of its own
+ * (run_parallel); run(i) finds that device current.  The thread-local error
+ * text of a failing item is carried to the caller's thread, and the first
+ * failing item's status returns, its text behind "`what` i (device d): " (no
+ * prefix where `what` is NULL). */
+static hhmm_status run_per_device(const std::vector<int> &devs, size_t n, const char *what,
+                                  const std::function<hhmm_status(size_t)> &run)
+{
+    std::vector<hhmm_status> st(n, HHMM_OK);
+    std::vector<std::string> msg(n);
+    run_parallel(n, [&](size_t i) {
+        const hipError_t e = hipSetDevice(devs[i]);
+        st[i] = e != hipSuccess ? hip_fail(e, "hipSetDevice") : run(i);
+        if (st[i] != HHMM_OK)
+            msg[i] = hhmm_last_error();
+    });
+    for (size_t i = 0; i < n; ++i)
+        if (st[i] != HHMM_OK) {
+            if (what)
+                set_error("%s %zu (device %d): %s", what, i, devs[i], msg[i].c_str());
+            else
+                set_error("%s", msg[i].c_str());
+            return st[i];
+        }
+    return HHMM_OK;
+}
+
+/* The end of a host request that ran: the pair statuses to the caller's
+ * array (optional), and the warning when any pair failed. */
+static hhmm_status report_pairs(const std::vector<int32_t> &status, int64_t P, int32_t *pair_status,
+                                const std::vector<int64_t> &fails)
+{
+    if (pair_status)
+        memcpy(pair_status, status.data(), (size_t)P * sizeof(int32_t));
+    int64_t failures = 0;
+    for (int64_t f : fails)
+        failures += f;
+    if (failures) {
+        set_error("%lld pair(s) hit an unset Viterbi back-pointer (Stan would throw)", (long long)failures);
+        return HHMM_WARN_PAIR_FAILURES;
+    }
     return HHMM_OK;
 }
 
@@ -1185,58 +841,20 @@ static hhmm_status run_on_device(const hhmm_request *req, hhmm_result *res, cons
  * set {GPU 0..7}, one host thread per GPU; §8e: contiguous series ranges). */
 static hhmm_status run_sharded(const hhmm_request *req, hhmm_result *res)
 {
-    std::vector<int> devs;
-    {
-        std::lock_guard<std::mutex> g(devset().mu);
-        devs = devset().devs.empty() ? std::vector<int>{0} : devset().devs;
-    }
+    const std::vector<int> devs = device_set();
     const std::vector<Shard> shards = make_shards(req, (int)devs.size());
     const int64_t P = npairs(req);
     std::vector<int32_t> status((size_t)P, 0);
-    std::vector<hhmm_status> st(shards.size(), HHMM_OK);
-    std::vector<std::string> msg(shards.size());
     std::vector<int64_t> fails(shards.size(), 0);
-    auto work = [&](size_t i) {
-        hipError_t e = hipSetDevice(devs[i]);
-        if (e != hipSuccess) {
-            st[i] = hip_fail(e, "hipSetDevice");
-        } else {
-            st[i] = run_on_device(req, res, shards[i], status.data(), &fails[i]);
-        }
-        if (st[i] != HHMM_OK)
-            msg[i] = hhmm_last_error(); /* thread-local: carried to the caller's thread */
-    };
-    std::vector<std::thread> th;
-    std::vector<size_t> mine{0};
-    for (size_t i = 1; i < shards.size(); ++i) {
-        try {
-            th.emplace_back(work, i);
-        } catch (...) { /* no exception crosses the C ABI: this thread runs that shard too */
-            mine.push_back(i);
-        }
-    }
     int cur = 0;
     (void)hipGetDevice(&cur);
-    for (size_t i : mine)
-        work(i);
-    for (auto &t : th)
-        t.join();
+    const hhmm_status s = run_per_device(devs, shards.size(), "shard", [&](size_t i) {
+        return run_on_device(req, res, shards[i], status.data(), &fails[i]);
+    });
     (void)hipSetDevice(cur);
-    for (size_t i = 0; i < shards.size(); ++i)
-        if (st[i] != HHMM_OK) {
-            set_error("shard %zu (device %d): %s", i, devs[i], msg[i].c_str());
-            return st[i];
-        }
-    if (res->pair_status)
-        memcpy(res->pair_status, status.data(), (size_t)P * sizeof(int32_t));
-    int64_t failures = 0;
-    for (int64_t f : fails)
-        failures += f;
-    if (failures) {
-        set_error("%lld pair(s) hit an unset Viterbi back-pointer (Stan would throw)", (long long)failures);
-        return HHMM_WARN_PAIR_FAILURES;
-    }
-    return HHMM_OK;
+    if (s != HHMM_OK)
+        return s;
+    return report_pairs(status, P, res->pair_status, fails);
 }
 
 /* ---------------- hhmm_run_summary: run, reduce over draws, download the summaries ----------------
@@ -1314,24 +932,6 @@ static SumPlan sum_plan(const hhmm_request *r, const hhmm_summary_spec *sp, int6
     return p;
 }
 
-/* `n` contiguous ranges of the series [a0, a1) with all their draws (GRID:
- * every draw; BLOCK: the series' own blocks) -- never a split by draws. */
-static std::vector<Shard> series_ranges(const hhmm_request *r, int64_t a0, int64_t a1, int64_t n)
-{
-    const int64_t N = r->data.n_series, S = r->draws.n_draws, P = npairs(r);
-    const int64_t B = r->pairing == HHMM_PAIR_BLOCK ? S / N : 0;
-    n = std::max<int64_t>(1, std::min(n, a1 - a0));
-    std::vector<Shard> v;
-    for (int64_t i = 0; i < n; ++i) {
-        const int64_t a = a0 + (a1 - a0) * i / n, b = a0 + (a1 - a0) * (i + 1) / n;
-        if (r->pairing == HHMM_PAIR_BLOCK)
-            v.push_back(Shard{{a, B * a, B * a}, {b - a, B * (b - a), B * (b - a)}, {N, S, P}});
-        else
-            v.push_back(Shard{{a, 0, S * a}, {b - a, S, S * (b - a)}, {N, S, P}});
-    }
-    return v;
-}
-
 /* Series [a0, a1) of the request on the current device.  `full`: the result
  * describe() sees (the caller's [P] pointers; placeholders, never
  * dereferenced, for the per-step outputs, which exist on the device only). */
@@ -1349,10 +949,8 @@ static hhmm_status run_summary_on_device(const hhmm_request *req, const hhmm_sum
     std::vector<ArrayDesc> arrays;
     describe(req, full, &dreq, &dres, arrays);
     const hhmm_data &d = req->data;
-    const int64_t Pw = npairs(req), N = d.n_series;
-    const bool seq = scan_plan(req->model, d.K, d.T_max, Pw, req->outputs, (uint32_t)req->flags).cl == 0 &&
-                     vscan_chunks(req->model, d.K, req->model == HHMM_MODEL_TAYAL_LITE ? d.T_oos_max : d.T_max, Pw,
-                                  req->outputs, (uint32_t)req->flags) == 0;
+    const int64_t N = d.n_series;
+    const bool seq = runs_sequentially(req);
     const int64_t forced = (int64_t)(((uint32_t)req->flags >> 20) & 0xffu);
     size_t freeb = 0, totalb = 0;
     if ((e = hipMemGetInfo(&freeb, &totalb)) != hipSuccess)
@@ -1392,13 +990,13 @@ static hhmm_status run_summary_on_device(const hhmm_request *req, const hhmm_sum
         }
     }
     if (seq && (ranges.size() > 1 || split_outside))
-        dreq.flags |= (int32_t)(HHMM_FLAG_SCAN_OFF | HHMM_FLAG_VIT_SCAN_OFF);
+        dreq.flags |= kSequentialFlags;
 
     /* the [P] outputs among `arrays`, and their place behind the summaries in the download slot */
     std::vector<size_t> pair_arrays;
     for (size_t i = 0; i < arrays.size(); ++i)
-        if (arrays[i].output && (arrays[i].dev_slot == (void **)&dres.loglik ||
-                                 arrays[i].dev_slot == (void **)&dres.logp_zstar))
+        if (arrays[i].output && (arrays[i].field == offsetof(hhmm_result, loglik) ||
+                                 arrays[i].field == offsetof(hhmm_result, logp_zstar)))
             pair_arrays.push_back(i);
     std::vector<ChunkLayout> lay;
     std::vector<SumPlan> plans;
@@ -1468,12 +1066,7 @@ static hhmm_status run_summary_on_device(const hhmm_request *req, const hhmm_sum
         const ChunkLayout &L = lay[i];
         const SumPlan &pl = plans[i];
         const Shard &c = ranges[i];
-        for (size_t j = 0; j < arrays.size(); ++j) {
-            if (L.off[j] >= L.in_end)
-                continue;
-            const ShardRows r = shard_rows(arrays[j].host, arrays[j], c);
-            par_copy_rows((char *)hin + L.off[j], r.width, r.base, r.pitch, r.width, r.rows);
-        }
+        gather_chunk(arrays, L, hin);
         if ((e = hipMemcpyAsync(dslot, hin, L.in_end, hipMemcpyHostToDevice, st)) != hipSuccess)
             break;
         if (ragged) { /* steps past a series' end keep the caller's fill: they travel up and back */
@@ -1483,20 +1076,9 @@ static hhmm_status run_summary_on_device(const hhmm_request *req, const hhmm_sum
         }
         if ((e = hipMemsetAsync((char *)dslot + L.status_off, 0, (size_t)L.P * sizeof(int32_t), st)) != hipSuccess)
             break;
-        hhmm_request cr = dreq;
-        hhmm_result cq = dres;
-        cr.data.n_series = c.cnt[SERIES];
-        cr.draws.n_draws = c.cnt[DRAWS];
-        for (size_t j = 0; j < arrays.size(); ++j) { /* as run_on_device binds a chunk */
-            const char *slot_base = (const char *)arrays[j].dev_slot;
-            void **f = nullptr;
-            if (slot_base >= (const char *)&dreq && slot_base < (const char *)(&dreq + 1))
-                f = (void **)((char *)&cr + (slot_base - (const char *)&dreq));
-            else
-                f = (void **)((char *)&cq + (slot_base - (const char *)&dres));
-            *f = (char *)dslot + L.off[j];
-        }
-        cq.pair_status = (int32_t *)((char *)dslot + L.status_off);
+        hhmm_request cr;
+        hhmm_result cq;
+        bind_chunk(arrays, L, dslot, dreq, dres, cr, cq);
         if ((ls = launch_all(&cr, &cq, L.P, ws, st)) != HHMM_OK)
             break;
         for (int b = 0; b < 32 && ls == HHMM_OK; ++b) {
@@ -1546,19 +1128,11 @@ static hhmm_status run_summary_on_device(const hhmm_request *req, const hhmm_sum
         }
         const int32_t *q = (const int32_t *)((char *)hout + ho);
         memcpy(status + c.off[PAIRS], q, (size_t)L.P * 4);
-        for (int64_t p = 0; p < L.P; ++p)
-            fails += q[p] != 0;
+        fails += count_nonzero(q, L.P);
     }
-    if (ls != HHMM_OK || e != hipSuccess) {
-        const std::string first = hhmm_last_error();
-        const hipError_t dr = sync_request(st); /* nothing of this request still runs when its buffers are pooled again */
-        cleanup();
-        if (ls == HHMM_OK)
-            return hip_fail(e, "summary run (copy or kernel execution)");
-        if (dr != hipSuccess)
-            set_error("%s; draining the request's stream then failed: %s", first.c_str(), hipGetErrorString(dr));
-        return ls;
-    }
+    if (ls != HHMM_OK || e != hipSuccess) /* nothing of this request still runs when its buffers are pooled again */
+        return fail_drained(ls, e, [&]() { return sync_request(st); }, cleanup,
+                            "summary run (copy or kernel execution)", "stream");
     cleanup();
     *failures = fails;
     return HHMM_OK;
@@ -1570,8 +1144,7 @@ static hhmm_status run_summary(const hhmm_request *req, const hhmm_summary_spec 
     const int64_t P = npairs(req), N = req->data.n_series;
     std::vector<int> devs;
     if (req->device == HHMM_DEVICE_SET) {
-        std::lock_guard<std::mutex> g(devset().mu);
-        devs = devset().devs.empty() ? std::vector<int>{0} : devset().devs;
+        devs = device_set();
     } else {
         int dev = req->device;
         if (dev < 0 && hipGetDevice(&dev) != hipSuccess)
@@ -1580,52 +1153,82 @@ static hhmm_status run_summary(const hhmm_request *req, const hhmm_summary_spec 
     }
     const size_t ns = (size_t)std::min<int64_t>(N, (int64_t)devs.size()); /* series ranges only, never draws */
     std::vector<int32_t> status((size_t)P, 0);
-    std::vector<hhmm_status> st(ns, HHMM_OK);
-    std::vector<std::string> msg(ns);
     std::vector<int64_t> fails(ns, 0);
     int cur = 0;
     (void)hipGetDevice(&cur);
-    auto work = [&](size_t i) {
-        const hipError_t e = hipSetDevice(devs[i]);
-        if (e != hipSuccess)
-            st[i] = hip_fail(e, "hipSetDevice");
-        else
-            st[i] = run_summary_on_device(req, spec, full, out, N * (int64_t)i / (int64_t)ns,
-                                          N * (int64_t)(i + 1) / (int64_t)ns, ns > 1, status.data(), &fails[i]);
-        if (st[i] != HHMM_OK)
-            msg[i] = hhmm_last_error();
-    };
-    std::vector<std::thread> th;
-    std::vector<size_t> mine{0};
-    for (size_t i = 1; i < ns; ++i) {
-        try {
-            th.emplace_back(work, i);
-        } catch (...) { /* no exception crosses the C ABI: this thread runs that range too */
-            mine.push_back(i);
-        }
-    }
-    for (size_t i : mine)
-        work(i);
-    for (auto &t : th)
-        t.join();
+    const hhmm_status s = run_per_device(devs, ns, ns > 1 ? "range" : nullptr, [&](size_t i) {
+        return run_summary_on_device(req, spec, full, out, N * (int64_t)i / (int64_t)ns,
+                                     N * (int64_t)(i + 1) / (int64_t)ns, ns > 1, status.data(), &fails[i]);
+    });
     if (req->device == HHMM_DEVICE_SET)
         (void)hipSetDevice(cur);
-    for (size_t i = 0; i < ns; ++i)
-        if (st[i] != HHMM_OK) {
-            if (ns > 1)
-                set_error("range %zu (device %d): %s", i, devs[i], msg[i].c_str());
-            else
-                set_error("%s", msg[i].c_str());
-            return st[i];
+    if (s != HHMM_OK)
+        return s;
+    return report_pairs(status, P, pairs ? pairs->pair_status : nullptr, fails);
+}
+
+template <class T> static void add_one(char *e, size_t n)
+{
+    for (size_t k = 0; k < n; ++k, e += sizeof(T)) {
+        T v;
+        memcpy(&v, e, sizeof(T));
+        v += 1;
+        memcpy(e, &v, sizeof(T));
+    }
+}
+
+/* The host staging of hhmm_run without a device: every shard of `nshards`
+ * cut into `nchunks` chunks, each chunk gathered into a heap slot (checked
+ * byte for byte against a row-by-row pack of the same slices), "run" (every
+ * output element + 1, every pair status 1) and scattered back -- through the
+ * gather_chunk / scatter_chunk that run_on_device calls.  outputs_up: the
+ * outputs are staged up whatever the request (else as hhmm_run does: when it
+ * is ragged); status: where the pair statuses go (NULL: nowhere). */
+static hhmm_status selftest_staging(const hhmm_request *req, hhmm_result *res, int nshards, int nchunks,
+                                    bool outputs_up, int32_t *status)
+{
+    hhmm_request dreq = *req;
+    hhmm_result dres = *res;
+    std::vector<ArrayDesc> arrays;
+    describe(req, res, &dreq, &dres, arrays);
+    const bool ragged = outputs_up || req->data.T != nullptr || req->data.T_oos != nullptr;
+    for (const Shard &sh : make_shards(req, nshards)) {
+        for (const Shard &c : split_shard(req, sh, nchunks)) {
+            const ChunkLayout L = chunk_layout(req, arrays, c, ragged);
+            if (L.P < 1 || !chunk_pairs_agree(req, c, L)) { /* run_on_device's guard */
+                set_error("pipeline self-test: a chunk stages %lld pairs for a sub-request of %lld",
+                          (long long)chunk_staged_pairs(req, c), (long long)L.P);
+                return HHMM_ERR_INVALID_ARGUMENT;
+            }
+            std::vector<char> slot(L.total, 0);
+            gather_chunk(arrays, L, slot.data());
+            for (size_t i = 0; i < arrays.size(); ++i) {
+                const ArrayDesc &a = arrays[i];
+                if (L.off[i] >= L.in_end)
+                    continue;
+                std::vector<char> ref(shard_bytes(a, L.sh));
+                copy_shard_host(ref.data(), a.host, a, L.sh, true);
+                if (memcmp(ref.data(), slot.data() + L.off[i], ref.size()) != 0) {
+                    set_error("pipeline self-test: the staged slice of an input differs");
+                    return HHMM_ERR_INVALID_ARGUMENT;
+                }
+            }
+            for (size_t i = 0; i < arrays.size(); ++i) /* the "kernel" */
+                if (arrays[i].output) {
+                    const size_t n = shard_bytes(arrays[i], L.sh) / arrays[i].esize;
+                    if (arrays[i].esize == sizeof(double))
+                        add_one<double>(slot.data() + L.off[i], n);
+                    else
+                        add_one<int32_t>(slot.data() + L.off[i], n);
+                }
+            add_one<int32_t>(slot.data() + L.status_off, (size_t)L.P); /* the slot is zeroed: status 1 */
+            const int64_t bad = scatter_chunk(arrays, L, slot.data() + L.out_begin, status, npairs(req));
+            if (bad != L.P) {
+                set_error("pipeline self-test: the scatter counted %lld failed pairs of %lld", (long long)bad,
+                          (long long)L.P);
+                return HHMM_ERR_INVALID_ARGUMENT;
+            }
         }
-    if (pairs && pairs->pair_status)
-        memcpy(pairs->pair_status, status.data(), (size_t)P * sizeof(int32_t));
-    int64_t failures = 0;
-    for (int64_t f : fails)
-        failures += f;
-    if (failures) {
-        set_error("%lld pair(s) hit an unset Viterbi back-pointer (Stan would throw)", (long long)failures);
-        return HHMM_WARN_PAIR_FAILURES;
     }
     return HHMM_OK;
 }
@@ -1738,17 +1341,11 @@ hhmm_status hhmm_run(const hhmm_request *req, hhmm_result *res)
         return hip_fail(e, "hipSetDevice");
     const int64_t P = npairs(req);
     std::vector<int32_t> status((size_t)P, 0);
-    int64_t failures = 0;
-    s = run_on_device(req, res, whole_shard(req), status.data(), &failures);
+    std::vector<int64_t> fails(1, 0);
+    s = run_on_device(req, res, whole_shard(req), status.data(), &fails[0]);
     if (s != HHMM_OK)
         return s;
-    if (res->pair_status)
-        memcpy(res->pair_status, status.data(), (size_t)P * sizeof(int32_t));
-    if (failures) {
-        set_error("%lld pair(s) hit an unset Viterbi back-pointer (Stan would throw)", (long long)failures);
-        return HHMM_WARN_PAIR_FAILURES;
-    }
-    return HHMM_OK;
+    return report_pairs(status, P, res->pair_status, fails);
 }
 
 hhmm_status hhmm_run_summary(const hhmm_request *req, const hhmm_summary_spec *spec, hhmm_result *pairs,
@@ -1812,8 +1409,7 @@ hhmm_status hhmm_run_summary(const hhmm_request *req, const hhmm_summary_spec *s
 
 int hhmm_device_set(int32_t *ordinals, int capacity)
 {
-    std::lock_guard<std::mutex> g(devset().mu);
-    const std::vector<int> d = devset().devs.empty() ? std::vector<int>{0} : devset().devs;
+    const std::vector<int> d = device_set();
     for (int i = 0; i < (int)d.size() && i < capacity; ++i)
         if (ordinals)
             ordinals[i] = d[(size_t)i];
@@ -1952,35 +1548,7 @@ hhmm_status hhmm_selftest_shards(const hhmm_request *req, hhmm_result *res, int 
         set_error("nshards must be >= 1");
         return HHMM_ERR_INVALID_ARGUMENT;
     }
-    hhmm_request dreq = *req;
-    hhmm_result dres = *res;
-    std::vector<ArrayDesc> arrays;
-    describe(req, res, &dreq, &dres, arrays);
-    for (const Shard &sh : make_shards(req, nshards)) {
-        for (const ArrayDesc &a : arrays) {
-            const ShardRows r = shard_rows(a.host, a, sh);
-            std::vector<char> packed(r.rows * r.width);
-            copy_shard_host(packed.data(), a.host, a, sh, true);
-            if (!a.output) /* inputs only travel host -> shard: back into a scratch twin */
-                continue;
-            const size_t n = packed.size() / a.esize;
-            for (size_t i = 0; i < n; ++i) {
-                if (a.esize == sizeof(double)) {
-                    double v;
-                    memcpy(&v, &packed[i * 8], 8);
-                    v += 1.0;
-                    memcpy(&packed[i * 8], &v, 8);
-                } else {
-                    int32_t v;
-                    memcpy(&v, &packed[i * 4], 4);
-                    v += 1;
-                    memcpy(&packed[i * 4], &v, 4);
-                }
-            }
-            copy_shard_host(packed.data(), a.host, a, sh, false);
-        }
-    }
-    return HHMM_OK;
+    return selftest_staging(req, res, nshards, 1, true, nullptr);
 }
 
 hhmm_status hhmm_selftest_pipeline(const hhmm_request *req, hhmm_result *res, int nshards, int nchunks)
@@ -1992,77 +1560,7 @@ hhmm_status hhmm_selftest_pipeline(const hhmm_request *req, hhmm_result *res, in
         set_error("nshards and nchunks must be >= 1");
         return HHMM_ERR_INVALID_ARGUMENT;
     }
-    hhmm_request dreq = *req;
-    hhmm_result dres = *res;
-    std::vector<ArrayDesc> arrays;
-    describe(req, res, &dreq, &dres, arrays);
-    const bool ragged = req->data.T != nullptr || req->data.T_oos != nullptr;
-    for (const Shard &sh : make_shards(req, nshards)) {
-        for (const Shard &c : split_shard(req, sh, nchunks)) {
-            const ChunkLayout L = chunk_layout(req, arrays, c, ragged);
-            if (L.P < 1 || !chunk_pairs_agree(req, c, L)) { /* run_on_device's guard */
-                set_error("pipeline self-test: a chunk stages %lld pairs for a sub-request of %lld",
-                          (long long)chunk_staged_pairs(req, c), (long long)L.P);
-                return HHMM_ERR_INVALID_ARGUMENT;
-            }
-            std::vector<char> slot(L.total, 0);
-            /* the gather, as run_on_device stages it, checked byte for byte
-             * against a row-by-row pack of the same slice */
-            for (size_t i = 0; i < arrays.size(); ++i) {
-                const ArrayDesc &a = arrays[i];
-                if (L.off[i] >= L.in_end)
-                    continue;
-                const ShardRows r = shard_rows(a.host, a, L.sh);
-                par_copy_rows(slot.data() + L.off[i], r.width, r.base, r.pitch, r.width, r.rows);
-                std::vector<char> ref(r.rows * r.width);
-                copy_shard_host(ref.data(), a.host, a, L.sh, true);
-                if (memcmp(ref.data(), slot.data() + L.off[i], ref.size()) != 0) {
-                    set_error("pipeline self-test: the staged slice of an input differs");
-                    return HHMM_ERR_INVALID_ARGUMENT;
-                }
-            }
-            /* the "kernel": every output element + 1, every pair status 1 */
-            for (size_t i = 0; i < arrays.size(); ++i) {
-                const ArrayDesc &a = arrays[i];
-                if (!a.output)
-                    continue;
-                const size_t n = shard_bytes(a, L.sh) / a.esize;
-                for (size_t k = 0; k < n; ++k) {
-                    char *e = slot.data() + L.off[i] + k * a.esize;
-                    if (a.esize == sizeof(double)) {
-                        double v;
-                        memcpy(&v, e, 8);
-                        v += 1.0;
-                        memcpy(e, &v, 8);
-                    } else {
-                        int32_t v;
-                        memcpy(&v, e, 4);
-                        v += 1;
-                        memcpy(e, &v, 4);
-                    }
-                }
-            }
-            for (int64_t q = 0; q < L.P; ++q) {
-                const int32_t one = 1;
-                memcpy(slot.data() + L.status_off + (size_t)q * 4, &one, 4);
-            }
-            /* the scatter of the downloaded region, as run_on_device runs it */
-            const char *down = slot.data() + L.out_begin;
-            for (size_t i = 0; i < arrays.size(); ++i) {
-                const ArrayDesc &a = arrays[i];
-                if (!a.output)
-                    continue;
-                const ShardRows r = shard_rows(a.host, a, L.sh);
-                par_copy_rows(r.base, r.pitch, down + (L.off[i] - L.out_begin), r.width, r.width, r.rows);
-            }
-            if (res->pair_status) {
-                const ArrayDesc sa{res->pair_status, nullptr, (size_t)npairs(req), sizeof(int32_t), true, PAIRS};
-                const ShardRows r = shard_rows(res->pair_status, sa, L.sh);
-                par_copy_rows(r.base, r.pitch, down + (L.status_off - L.out_begin), r.width, r.width, r.rows);
-            }
-        }
-    }
-    return HHMM_OK;
+    return selftest_staging(req, res, nshards, nchunks, false, res->pair_status);
 }
 
 hhmm_status hhmm_selftest_cr_log(const double *in, double *out, int64_t n)

@@ -1,9 +1,11 @@
-"""CPU: the device-set sharding of hhmm_run (HHMM_DEVICE_SET; hhmm_api.cpp
+"""CPU: the device-set sharding of hhmm_run (HHMM_DEVICE_SET; hhmm_stage.cpp
 make_shards / shard_rows) covers every output element exactly once, for every
 pairing, with draw splits (GRID with fewer series than shards), ragged T and
-every array class (series, draws, pairs).  hhmm_selftest_shards runs the
-shard plan and the slice copies on host buffers only, so this runs without a
-GPU -- and under host ASan / UBSan in tools/sanitize.sh."""
+every array class (series, draws, pairs).  hhmm_selftest_shards and
+hhmm_selftest_pipeline run the shard and chunk plan on host buffers only, and
+stage every chunk through the library's own gather_chunk and scatter_chunk --
+the functions hhmm_run's device path calls, not a copy of them -- so this runs
+without a GPU, and under host ASan / UBSan in tools/sanitize.sh."""
 import ctypes as C
 
 import numpy as np
