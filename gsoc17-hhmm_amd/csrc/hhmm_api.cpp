@@ -1740,28 +1740,168 @@ hhmm_status hhmm_extract_features(const hhmm_ticks *ticks, hhmm_legs *legs, int 
 
 /* ------------------------------------------------------------------ */
 /* Statistics per (series, draw) pair: the E-step (include/hhmm_estep.h), */
-/* the draw statistics (hhmm_gibbs.h, hhmm_gibbs_gauss.h) and the expected */
-/* draw statistics (hhmm_expect.h) share one host path                  */
+/* the draw statistics (hhmm_gibbs.h, hhmm_gibbs_gauss.h), the expected  */
+/* draw statistics (hhmm_expect.h) and the IOHMM E-step                 */
+/* (hhmm_estep_io.h) share one host path                                */
 /* ------------------------------------------------------------------ */
 
-/* What tells the four entries apart on the host. */
+/* One array of a host call: uploaded from host_in, or downloaded to host_out
+ * after the launch; *dev is its pointer inside the device-side request /
+ * result.  A row is live when its host pointer is non-NULL and it has bytes;
+ * the device pointer of every other row is NULL. */
+struct StatsArr {
+    const void *host_in;
+    void *host_out;
+    void **dev;
+    size_t bytes;
+};
+
+/* The device-side result of a host call, whichever struct the entry fills. */
+union StatsResult {
+    hhmm_estep_result estep;
+    hhmm_estep_io_result io;
+};
+
+/* What tells the entries apart on the host.  The result struct is the
+ * entry's own: the shared path only hands it on. */
 struct StatsEntry {
     const char *name; /* in messages */
     bool reads_u;     /* ffbs_u is an input (elsewhere the field is ignored) */
-    hhmm_status (*check)(const hhmm_request *, const hhmm_estep_result *);
-    hhmm_status (*launch)(const hhmm_request *, const hhmm_estep_result *, int64_t, void *, hipStream_t);
+    hhmm_status (*check)(const hhmm_request *, const void *);
+    hhmm_status (*launch)(const hhmm_request *, const void *, int64_t, void *, hipStream_t);
+    size_t (*workspace)(int K, int Tmax, int64_t P);
+    /* the arrays of a host call: req / res on the host, dr / dq their device-side copies */
+    void (*arrays)(const StatsEntry &en, const hhmm_request *req, const void *res, hhmm_request *dr, StatsResult *dq,
+                   std::vector<StatsArr> &arrs);
 };
-static const StatsEntry kEstep = {"E-step", false, check_estep, launch_estep};
-static const StatsEntry kDrawStats = {"draw statistics", true, check_draw_stats, launch_draw_stats};
-static const StatsEntry kDrawStatsGauss = {"Gaussian draw statistics", true, check_draw_stats_gauss,
-                                           launch_draw_stats_gauss};
-static const StatsEntry kExpectedStats = {"expected statistics", false, check_expected_stats, launch_expected_stats};
+
+template <class R, hhmm_status (*F)(const hhmm_request *, const R *)>
+static hhmm_status typed_check(const hhmm_request *r, const void *o)
+{
+    return F(r, (const R *)o);
+}
+template <class R, hhmm_status (*F)(const hhmm_request *, const R *, int64_t, void *, hipStream_t)>
+static hhmm_status typed_launch(const hhmm_request *r, const void *o, int64_t P, void *ws, hipStream_t st)
+{
+    return F(r, (const R *)o, P, ws, st);
+}
+
+/* hhmm_estep_result: the HMM and Tayal families */
+static void estep_arrays(const StatsEntry &en, const hhmm_request *req, const void *res_, hhmm_request *dr_,
+                         StatsResult *dq_, std::vector<StatsArr> &arrs)
+{
+    const hhmm_estep_result *res = (const hhmm_estep_result *)res_;
+    hhmm_request &dr = *dr_;
+    hhmm_estep_result &dq = dq_->estep;
+    const hhmm_data &d = req->data;
+    const hhmm_draws &w = req->draws;
+    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max, K = (size_t)d.K;
+    const size_t P = (size_t)npairs(req);
+    const bool gauss = req->model == HHMM_MODEL_HMM_GAUSS; /* else one of the discrete programs */
+    const bool tayal = req->model == HHMM_MODEL_TAYAL;
+    const bool semisup = req->model == HHMM_MODEL_HMM_MULTINOM_SEMISUP;
+    const size_t L = gauss ? 0 : (size_t)d.L;
+    arrs = {
+        {d.T, nullptr, (void **)&dr.data.T, N * 4},
+        {gauss ? nullptr : d.x_int, nullptr, (void **)&dr.data.x_int, N * Tm * 4},
+        {gauss ? d.x_real : nullptr, nullptr, (void **)&dr.data.x_real, N * Tm * 8},
+        {semisup ? d.g : nullptr, nullptr, (void **)&dr.data.g, N * Tm * 4},
+        {tayal ? d.sign : nullptr, nullptr, (void **)&dr.data.sign, N * Tm * 4},
+        {tayal ? nullptr : w.p_1k, nullptr, (void **)&dr.draws.p_1k, S * K * 8},
+        {tayal ? nullptr : w.A_ij, nullptr, (void **)&dr.draws.A_ij, S * K * K * 8},
+        {tayal ? w.p_11 : nullptr, nullptr, (void **)&dr.draws.p_11, S * 8},
+        {tayal ? w.A_row : nullptr, nullptr, (void **)&dr.draws.A_row, S * 4 * 8},
+        {gauss ? nullptr : w.phi_k, nullptr, (void **)&dr.draws.phi_k, S * K * L * 8},
+        {gauss ? w.mu_k : nullptr, nullptr, (void **)&dr.draws.mu_k, S * K * 8},
+        {gauss ? w.sigma_k : nullptr, nullptr, (void **)&dr.draws.sigma_k, S * K * 8},
+        {en.reads_u ? req->ffbs_u : nullptr, nullptr, (void **)&dr.ffbs_u, P * Tm * 8},
+        {nullptr, res->loglik, (void **)&dq.loglik, P * 8},
+        {nullptr, res->n_1k, (void **)&dq.n_1k, P * K * 8},
+        {nullptr, res->xi_ij, (void **)&dq.xi_ij, P * K * K * 8},
+        {nullptr, gauss ? nullptr : res->c_kl, (void **)&dq.c_kl, P * K * L * 8},
+        {nullptr, gauss ? res->w_k : nullptr, (void **)&dq.w_k, P * K * 8},
+        {nullptr, gauss ? res->s1_k : nullptr, (void **)&dq.s1_k, P * K * 8},
+        {nullptr, gauss ? res->s2_k : nullptr, (void **)&dq.s2_k, P * K * 8},
+        {nullptr, res->pair_status, (void **)&dq.pair_status, P * 4},
+    };
+}
+
+/* hhmm_estep_io_result: the IOHMM programs */
+static void estep_io_arrays(const StatsEntry &, const hhmm_request *req, const void *res_, hhmm_request *dr_,
+                            StatsResult *dq_, std::vector<StatsArr> &arrs)
+{
+    const hhmm_estep_io_result *res = (const hhmm_estep_io_result *)res_;
+    hhmm_request &dr = *dr_;
+    hhmm_estep_io_result &dq = dq_->io;
+    const hhmm_data &d = req->data;
+    const hhmm_draws &w = req->draws;
+    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max, K = (size_t)d.K;
+    const size_t P = (size_t)npairs(req), M = (size_t)d.M;
+    const bool reg = req->model == HHMM_MODEL_IOHMM_REG; /* else one of the mixture programs */
+    const size_t L = reg ? 0 : (size_t)d.L;
+    arrs = {
+        {d.T, nullptr, (void **)&dr.data.T, N * 4},
+        {d.x_real, nullptr, (void **)&dr.data.x_real, N * Tm * 8},
+        {d.u, nullptr, (void **)&dr.data.u, N * Tm * M * 8},
+        {w.p_1k, nullptr, (void **)&dr.draws.p_1k, S * K * 8},
+        {w.w_km, nullptr, (void **)&dr.draws.w_km, S * K * M * 8},
+        {reg ? w.b_km : nullptr, nullptr, (void **)&dr.draws.b_km, S * K * M * 8},
+        {reg ? w.s_k : nullptr, nullptr, (void **)&dr.draws.s_k, S * K * 8},
+        {reg ? nullptr : w.lambda_kl, nullptr, (void **)&dr.draws.lambda_kl, S * K * L * 8},
+        {reg ? nullptr : w.mu_kl, nullptr, (void **)&dr.draws.mu_kl, S * K * L * 8},
+        {reg ? nullptr : w.s_kl, nullptr, (void **)&dr.draws.s_kl, S * K * L * 8},
+        {nullptr, res->loglik, (void **)&dq.loglik, P * 8},
+        {nullptr, res->n_1k, (void **)&dq.n_1k, P * K * 8},
+        {nullptr, res->gw_km, (void **)&dq.gw_km, P * K * M * 8},
+        {nullptr, reg ? res->n_k : nullptr, (void **)&dq.n_k, P * K * 8},
+        {nullptr, reg ? res->uu_kmm : nullptr, (void **)&dq.uu_kmm, P * K * M * M * 8},
+        {nullptr, reg ? res->ux_km : nullptr, (void **)&dq.ux_km, P * K * M * 8},
+        {nullptr, reg ? res->xx_k : nullptr, (void **)&dq.xx_k, P * K * 8},
+        {nullptr, reg ? nullptr : res->n_kl, (void **)&dq.n_kl, P * K * L * 8},
+        {nullptr, reg ? nullptr : res->sx_kl, (void **)&dq.sx_kl, P * K * L * 8},
+        {nullptr, reg ? nullptr : res->sxx_kl, (void **)&dq.sxx_kl, P * K * L * 8},
+        {nullptr, res->pair_status, (void **)&dq.pair_status, P * 4},
+    };
+}
+
+static size_t no_workspace(int, int, int64_t) { return 0; }
+
+static const StatsEntry kEstep = {"E-step",
+                                  false,
+                                  typed_check<hhmm_estep_result, check_estep>,
+                                  typed_launch<hhmm_estep_result, launch_estep>,
+                                  estep_workspace_bytes,
+                                  estep_arrays};
+static const StatsEntry kDrawStats = {"draw statistics",
+                                      true,
+                                      typed_check<hhmm_estep_result, check_draw_stats>,
+                                      typed_launch<hhmm_estep_result, launch_draw_stats>,
+                                      estep_workspace_bytes,
+                                      estep_arrays};
+static const StatsEntry kDrawStatsGauss = {"Gaussian draw statistics",
+                                           true,
+                                           typed_check<hhmm_estep_result, check_draw_stats_gauss>,
+                                           typed_launch<hhmm_estep_result, launch_draw_stats_gauss>,
+                                           estep_workspace_bytes,
+                                           estep_arrays};
+static const StatsEntry kExpectedStats = {"expected statistics",
+                                          false,
+                                          typed_check<hhmm_estep_result, check_expected_stats>,
+                                          typed_launch<hhmm_estep_result, launch_expected_stats>,
+                                          estep_workspace_bytes,
+                                          estep_arrays};
+static const StatsEntry kEstepIo = {"IOHMM E-step",
+                                    false,
+                                    typed_check<hhmm_estep_io_result, check_estep_io>,
+                                    typed_launch<hhmm_estep_io_result, launch_estep_io>,
+                                    no_workspace,
+                                    estep_io_arrays};
 
 /* Argument checks of the device and the host entry, none of which needs a
  * device: the entry's own scope first (HHMM_ERR_UNSUPPORTED names the reason),
  * then the request as hhmm_run / hhmm_run_device check it (host: the
  * data-block bounds too). */
-static hhmm_status stats_check(const StatsEntry &en, const hhmm_request *req, const hhmm_estep_result *res, bool host)
+static hhmm_status stats_check(const StatsEntry &en, const hhmm_request *req, const void *res, bool host)
 {
     hhmm_status s = en.check(req, res);
     if (s != HHMM_OK)
@@ -1789,11 +1929,11 @@ static hhmm_status stats_workspace_size(const StatsEntry &en, const hhmm_request
         set_error("%s: K = %d, the lane-per-pair kernel supports K <= %d", en.name, req->data.K, kMaxK);
         return HHMM_ERR_UNSUPPORTED;
     }
-    *bytes = estep_workspace_bytes(req->data.K, req->data.T_max, P);
+    *bytes = en.workspace(req->data.K, req->data.T_max, P);
     return HHMM_OK;
 }
 
-static hhmm_status stats_device(const StatsEntry &en, const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+static hhmm_status stats_device(const StatsEntry &en, const hhmm_request *req, const void *res, void *workspace,
                                 size_t workspace_bytes_, void *stream)
 {
     hhmm_status s = stats_check(en, req, res, false);
@@ -1802,15 +1942,15 @@ static hhmm_status stats_device(const StatsEntry &en, const hhmm_request *req, h
     if ((s = check_device()) != HHMM_OK)
         return s;
     const int64_t P = npairs(req);
-    const size_t need = estep_workspace_bytes(req->data.K, req->data.T_max, P);
-    if (workspace_bytes_ < need || !workspace) {
+    const size_t need = en.workspace(req->data.K, req->data.T_max, P);
+    if (workspace_bytes_ < need || (need && !workspace)) {
         set_error("workspace of %zu bytes < %zu required", workspace_bytes_, need);
         return HHMM_ERR_INVALID_ARGUMENT;
     }
     return en.launch(req, res, P, workspace, (hipStream_t)stream);
 }
 
-static hhmm_status stats_host(const StatsEntry &en, const hhmm_request *req, hhmm_estep_result *res)
+static hhmm_status stats_host(const StatsEntry &en, const hhmm_request *req, const void *res)
 {
     hhmm_status s = stats_check(en, req, res, true);
     if (s != HHMM_OK)
@@ -1824,54 +1964,20 @@ static hhmm_status stats_host(const StatsEntry &en, const hhmm_request *req, hhm
     if (e != hipSuccess)
         return hip_fail(e, "hipSetDevice");
     const hhmm_data &d = req->data;
-    const hhmm_draws &w = req->draws;
-    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max, K = (size_t)d.K;
     const size_t P = (size_t)npairs(req);
-    const bool gauss = req->model == HHMM_MODEL_HMM_GAUSS; /* else one of the discrete programs */
-    const bool tayal = req->model == HHMM_MODEL_TAYAL;
-    const bool semisup = req->model == HHMM_MODEL_HMM_MULTINOM_SEMISUP;
-    const size_t L = gauss ? 0 : (size_t)d.L;
     hhmm_request dr = *req;
-    hhmm_estep_result dq{};
-    /* a row is live when its host pointer is non-NULL and it has bytes; the
-     * device pointer of every other row is NULL */
-    struct Arr {
-        const void *host_in;
-        void *host_out;
-        void **dev;
-        size_t bytes;
-    } arrs[] = {
-        {d.T, nullptr, (void **)&dr.data.T, N * 4},
-        {gauss ? nullptr : d.x_int, nullptr, (void **)&dr.data.x_int, N * Tm * 4},
-        {gauss ? d.x_real : nullptr, nullptr, (void **)&dr.data.x_real, N * Tm * 8},
-        {semisup ? d.g : nullptr, nullptr, (void **)&dr.data.g, N * Tm * 4},
-        {tayal ? d.sign : nullptr, nullptr, (void **)&dr.data.sign, N * Tm * 4},
-        {tayal ? nullptr : w.p_1k, nullptr, (void **)&dr.draws.p_1k, S * K * 8},
-        {tayal ? nullptr : w.A_ij, nullptr, (void **)&dr.draws.A_ij, S * K * K * 8},
-        {tayal ? w.p_11 : nullptr, nullptr, (void **)&dr.draws.p_11, S * 8},
-        {tayal ? w.A_row : nullptr, nullptr, (void **)&dr.draws.A_row, S * 4 * 8},
-        {gauss ? nullptr : w.phi_k, nullptr, (void **)&dr.draws.phi_k, S * K * L * 8},
-        {gauss ? w.mu_k : nullptr, nullptr, (void **)&dr.draws.mu_k, S * K * 8},
-        {gauss ? w.sigma_k : nullptr, nullptr, (void **)&dr.draws.sigma_k, S * K * 8},
-        {en.reads_u ? req->ffbs_u : nullptr, nullptr, (void **)&dr.ffbs_u, P * Tm * 8},
-        {nullptr, res->loglik, (void **)&dq.loglik, P * 8},
-        {nullptr, res->n_1k, (void **)&dq.n_1k, P * K * 8},
-        {nullptr, res->xi_ij, (void **)&dq.xi_ij, P * K * K * 8},
-        {nullptr, gauss ? nullptr : res->c_kl, (void **)&dq.c_kl, P * K * L * 8},
-        {nullptr, gauss ? res->w_k : nullptr, (void **)&dq.w_k, P * K * 8},
-        {nullptr, gauss ? res->s1_k : nullptr, (void **)&dq.s1_k, P * K * 8},
-        {nullptr, gauss ? res->s2_k : nullptr, (void **)&dq.s2_k, P * K * 8},
-        {nullptr, res->pair_status, (void **)&dq.pair_status, P * 4},
-    };
+    StatsResult dq{};
+    std::vector<StatsArr> arrs;
+    en.arrays(en, req, res, &dr, &dq, arrs);
     /* one pooled block: every array at a 256-byte boundary, then the workspace */
     size_t total = 0;
     std::vector<size_t> off;
-    for (const Arr &a : arrs) {
+    for (const StatsArr &a : arrs) {
         off.push_back(total);
         if ((a.host_in || a.host_out) && a.bytes)
             total += (a.bytes + 255) & ~(size_t)255;
     }
-    const size_t wsb = estep_workspace_bytes(d.K, d.T_max, (int64_t)P);
+    const size_t wsb = en.workspace(d.K, d.T_max, (int64_t)P);
     char *blk = (char *)pool_get(dev, total);
     void *ws = pool_get(dev, wsb);
     auto cleanup = [&]() {
@@ -1883,8 +1989,8 @@ static hhmm_status stats_host(const StatsEntry &en, const hhmm_request *req, hhm
         set_error("device %d: %s allocation of %zu + %zu bytes failed", dev, en.name, total, wsb);
         return HHMM_ERR_OUT_OF_MEMORY;
     }
-    for (size_t i = 0; i < sizeof(arrs) / sizeof(arrs[0]) && e == hipSuccess; ++i) {
-        const Arr &a = arrs[i];
+    for (size_t i = 0; i < arrs.size() && e == hipSuccess; ++i) {
+        const StatsArr &a = arrs[i];
         const bool used = (a.host_in || a.host_out) && a.bytes;
         *a.dev = used ? (void *)(blk + off[i]) : nullptr;
         if (used && a.host_in)
@@ -1897,7 +2003,7 @@ static hhmm_status stats_host(const StatsEntry &en, const hhmm_request *req, hhm
     s = en.launch(&dr, &dq, (int64_t)P, ws, nullptr);
     e = hipStreamSynchronize(nullptr); /* before the pooled blocks can go to another request */
     if (s == HHMM_OK && e == hipSuccess)
-        for (const Arr &a : arrs)
+        for (const StatsArr &a : arrs)
             if (a.host_out && a.bytes && e == hipSuccess)
                 e = hipMemcpy(a.host_out, *a.dev, a.bytes, hipMemcpyDeviceToHost);
     cleanup();
@@ -1961,6 +2067,20 @@ hhmm_status hhmm_expected_stats_device(const hhmm_request *req, hhmm_estep_resul
 hhmm_status hhmm_expected_stats(const hhmm_request *req, hhmm_estep_result *res)
 {
     return stats_host(kExpectedStats, req, res);
+}
+
+hhmm_status hhmm_estep_io_workspace_size(const hhmm_request *req, size_t *bytes)
+{
+    return stats_workspace_size(kEstepIo, req, bytes);
+}
+hhmm_status hhmm_estep_io_device(const hhmm_request *req, hhmm_estep_io_result *res, void *workspace,
+                                 size_t workspace_bytes_, void *stream)
+{
+    return stats_device(kEstepIo, req, res, workspace, workspace_bytes_, stream);
+}
+hhmm_status hhmm_estep_io(const hhmm_request *req, hhmm_estep_io_result *res)
+{
+    return stats_host(kEstepIo, req, res);
 }
 
 } // extern "C"

@@ -1,10 +1,12 @@
 /*
- * hhmm_stats.h -- host-side pieces shared by the four "statistics per
- * (series, draw) pair" entries: the E-step (hhmm_estep.hip), the draw
- * statistics (hhmm_draw_stats.hip, hhmm_draw_stats_gauss.hip) and the expected
- * draw statistics (hhmm_expect.hip).  The kernels differ; the argument checks,
- * the DevArgs of a launch, the LDS fit, the dispatch on K and the launch
- * epilogue do not.  Not part of the public ABI.
+ * hhmm_stats.h -- host-side pieces shared by the "statistics per (series,
+ * draw) pair" entries: the E-step (hhmm_estep.hip), the draw statistics
+ * (hhmm_draw_stats.hip, hhmm_draw_stats_gauss.hip), the expected draw
+ * statistics (hhmm_expect.hip) and the IOHMM E-step (hhmm_estep_io.hip).  The
+ * kernels differ; the argument checks, the DevArgs of a launch, the LDS fit,
+ * the dispatch on K and the launch epilogue do not.  stats_check_tail belongs
+ * to the four entries that fill an hhmm_estep_result; the IOHMM E-step has a
+ * result struct and a tail of its own.  Not part of the public ABI.
  */
 #pragma once
 #include <type_traits>

@@ -222,6 +222,23 @@ class EstepResult(C.Structure):
     ]
 
 
+# include/hhmm_estep_io.h
+class EstepIoResult(C.Structure):
+    _fields_ = [
+        ("loglik", C.c_void_p),
+        ("n_1k", C.c_void_p),
+        ("gw_km", C.c_void_p),
+        ("n_k", C.c_void_p),
+        ("uu_kmm", C.c_void_p),
+        ("ux_km", C.c_void_p),
+        ("xx_k", C.c_void_p),
+        ("n_kl", C.c_void_p),
+        ("sx_kl", C.c_void_p),
+        ("sxx_kl", C.c_void_p),
+        ("pair_status", C.c_void_p),
+    ]
+
+
 # Data-block fields (name -> (ctype kind, shape code)).  Shape codes use
 # N = series, T = T_max, M, To = T_oos_max.
 DATA_ARRAYS = {
@@ -348,4 +365,12 @@ def declare(lib):
     lib.hhmm_expected_stats_device.restype = C.c_int
     lib.hhmm_expected_stats.argtypes = [RP, EP]
     lib.hhmm_expected_stats.restype = C.c_int
+    # include/hhmm_estep_io.h
+    IP = C.POINTER(EstepIoResult)
+    lib.hhmm_estep_io_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
+    lib.hhmm_estep_io_workspace_size.restype = C.c_int
+    lib.hhmm_estep_io_device.argtypes = [RP, IP, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.hhmm_estep_io_device.restype = C.c_int
+    lib.hhmm_estep_io.argtypes = [RP, IP]
+    lib.hhmm_estep_io.restype = C.c_int
     return lib

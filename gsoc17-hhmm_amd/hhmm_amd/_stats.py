@@ -1,8 +1,8 @@
 """What the "statistics per (series, draw) pair" entries share on the Python side.
 
 hhmm_estep, hhmm_draw_stats, hhmm_draw_stats_gauss and hhmm_expected_stats take
-an hhmm_request and fill an hhmm_estep_result (include/hhmm_estep.h); they
-differ in the draw arrays they read, the statistics they return and whether
+an hhmm_request and fill an hhmm_estep_result (include/hhmm_estep.h);
+hhmm_estep_io fills its own hhmm_estep_io_result (`result_cls`).  They differ in the draw arrays they read, the statistics they return and whether
 they consume uniforms.  `request()` builds the pair with the shape checks,
 `add_uniforms()` attaches the uniforms of a draw, `call()` runs a host entry,
 and `DeviceStats` keeps a prepared request on the GPU for repeated calls of a
@@ -16,8 +16,8 @@ from . import _abi
 from .api import HHMMError, PreparedRequest, _f64
 
 
-def request(model, data, draws, pairing, device, param_shapes, stat_shapes):
-    """(PreparedRequest, EstepResult, {name: array}) with the shape checks.
+def request(model, data, draws, pairing, device, param_shapes, stat_shapes, result_cls=_abi.EstepResult):
+    """(PreparedRequest, result_cls(), {name: array}) with the shape checks.
 
     param_shapes(S, K, L) and stat_shapes(P, K, L) return {name: shape} of the
     draw arrays the entry reads and of the statistics it returns."""
@@ -30,7 +30,7 @@ def request(model, data, draws, pairing, device, param_shapes, stat_shapes):
             raise ValueError(f"{model} needs the draw array {name}")
         if np.shape(draws[name]) != shape:
             raise ValueError(f"{name} must have shape {shape}, got {np.shape(draws[name])}")
-    res = _abi.EstepResult()
+    res = result_cls()
     out = {}
     for name, shape in stat_shapes(pr.P, pr.K, L).items():
         out[name] = np.full(shape, np.nan, dtype=np.float64, order="F")
