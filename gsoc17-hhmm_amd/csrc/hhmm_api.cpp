@@ -23,6 +23,7 @@
 
 #include "hhmm_internal.h"
 #include "hhmm_stage.h"
+#include "hhmm_stats.h"
 #include "build_id.h" /* HHMM_SOURCE_HASH (Makefile) */
 
 namespace hhmm {

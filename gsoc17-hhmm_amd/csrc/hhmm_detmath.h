@@ -30,11 +30,14 @@
  *     log m = 2 s + s^3 (2/3 + 2/5 s^2 + ... + 2/21 s^18) (truncation < 2^-60),
  *     + e ln2 (two parts).
  *
- * The includer defines HHMM_MATH_FN (see hhmm_crmath.h).  Both sides compile
+ * The includer defines HHMM_MATH_FN (see hhmm_crmath.h, included here for that
+ * and for hhmm_exp2_entry).  Both sides compile
  * with -ffp-contract=off, so no multiply-add is fused behind our back.
  */
 #pragma once
 #include <stdint.h>
+
+#include "hhmm_crmath.h"
 
 #define HHMM_DET_LN2_HI 0x1.62e42feep-1 /* 32 significant bits */
 #define HHMM_DET_LN2_LO 0x1.a39ef35793c76p-33

@@ -5,7 +5,8 @@
  * (state, symbol) pairs -- for hmm-multinom, semisup and Tayal at K <= 8.
  * Nothing is written per step.
  *
- * One LANE owns one pair (hhmm_hmm.h's layout, helpers and latency rules).
+ * One LANE owns one pair (the layout and latency rules of hhmm_step.h, the
+ * chunk helpers of hhmm_fbchunk.h).
  *   forward   the FFBS contract's filter, the operations of
  *             fb_kernel<.., FB_GAMMA | FB_FFBS> (fwd_chunk: per-step
  *             renormalisation, emit_prob<.., true>): a checkpoint every
@@ -30,7 +31,7 @@
 #include <math.h>
 
 #include "hhmm_gibbs.h"
-#include "hhmm_hmm.h"
+#include "hhmm_fbchunk.h"
 #include "hhmm_drawstep.h"
 #include "hhmm_stats.h"
 

@@ -32,7 +32,7 @@
 #include <math.h>
 
 #include "hhmm_gibbs_gauss.h"
-#include "hhmm_hmm.h"
+#include "hhmm_fbchunk.h"
 #include "hhmm_drawstep.h"
 #include "hhmm_stats.h"
 

@@ -4,7 +4,7 @@
  * copies of the transition matrix and the one-word LDS count.
  */
 #pragma once
-#include "hhmm_hmm.h"
+#include "hhmm_fbchunk.h"
 
 namespace hhmm {
 
@@ -21,7 +21,7 @@ __device__ __forceinline__ double opaque(double v)
     return v;
 }
 
-/* ffbs_draw (hhmm_hmm.h) with the mask of step t + 1 at z_{t+1} already decided
+/* ffbs_draw (hhmm_fbchunk.h) with the mask of step t + 1 at z_{t+1} already decided
  * (`on`): the same operations on the same values, so the same z.  The column
  * A(., z_{t+1}) is picked from opaque copies of the entries: left to itself
  * hipcc folds the select chain over pp.A into one dynamically indexed load,

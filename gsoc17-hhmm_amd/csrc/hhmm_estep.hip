@@ -4,7 +4,8 @@
  * steps -- gamma_1, the pairwise posterior sum xi_ij and the emission sums --
  * for hmm and hmm-multinom at K <= 8.  Nothing is written per step.
  *
- * One LANE owns one pair (hhmm_hmm.h's layout, helpers and latency rules).
+ * One LANE owns one pair (the layout and latency rules of hhmm_step.h, the
+ * chunk helpers of hhmm_fbchunk.h).
  *   forward   fb_kernel's scaled linear-space sweep (fwd_chunk): a checkpoint
  *             of alpha every C = fb_chunk(K) steps, loglik at the end.
  *   backward  chunk by chunk from the end: alpha over the chunk is recomputed
@@ -35,7 +36,7 @@
 #include <math.h>
 
 #include "hhmm_estep.h"
-#include "hhmm_hmm.h"
+#include "hhmm_fbchunk.h"
 #include "hhmm_stats.h"
 
 namespace hhmm {

@@ -32,7 +32,7 @@
 #include <math.h>
 
 #include "hhmm_expect.h"
-#include "hhmm_hmm.h"
+#include "hhmm_fbchunk.h"
 #include "hhmm_stats.h"
 
 namespace hhmm {

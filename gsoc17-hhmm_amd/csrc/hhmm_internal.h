@@ -11,11 +11,6 @@
 #include "hhmm.h"
 #include "hhmm_features.h"
 #include "hhmm_summary.h"
-#include "hhmm_estep.h"
-#include "hhmm_gibbs.h"
-#include "hhmm_gibbs_gauss.h"
-#include "hhmm_expect.h"
-#include "hhmm_estep_io.h"
 
 namespace hhmm {
 
@@ -219,41 +214,6 @@ void set_error(const char *fmt, ...);
  * and the launch on `st` (device pointers). */
 hhmm_status check_summary(const hhmm_summary_request *r, const double *quantiles, const int32_t *argmax);
 hhmm_status launch_summary(const hhmm_summary_request *r, double *quantiles, int32_t *argmax, hipStream_t st);
-
-/* The five "statistics per (series, draw) pair" entries below each give the
- * host path of hhmm_api.cpp (StatsEntry, stats_*) a check_* and a launch_*;
- * what those share among themselves is in hhmm_stats.h.
- *
- * Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
- * checkpoint workspace and the launch on `st` (device pointers). */
-hhmm_status check_estep(const hhmm_request *r, const hhmm_estep_result *o);
-size_t estep_workspace_bytes(int K, int Tmax, int64_t P);
-hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws, hipStream_t st);
-
-/* Draw statistics (hhmm_draw_stats.hip): argument checks (no device needed)
- * and the launch on `st` (device pointers); the workspace is the E-step's. */
-hhmm_status check_draw_stats(const hhmm_request *r, const hhmm_estep_result *o);
-hhmm_status launch_draw_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
-                              hipStream_t st);
-
-/* Gaussian draw statistics (hhmm_draw_stats_gauss.hip): the same pair for
- * hmm.stan; the workspace is the E-step's. */
-hhmm_status check_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_result *o);
-hhmm_status launch_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
-                                    hipStream_t st);
-
-/* Expected draw statistics (hhmm_expect.hip): argument checks (no device
- * needed) and the launch on `st` (device pointers); the workspace is the
- * E-step's, and hmm-multinom goes to launch_estep. */
-hhmm_status check_expected_stats(const hhmm_request *r, const hhmm_estep_result *o);
-hhmm_status launch_expected_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
-                                  hipStream_t st);
-
-/* IOHMM E-step (hhmm_estep_io.hip): argument checks (no device needed) and the
- * launch on `st` (device pointers); its own result struct, no workspace. */
-hhmm_status check_estep_io(const hhmm_request *r, const hhmm_estep_io_result *o);
-hhmm_status launch_estep_io(const hhmm_request *r, const hhmm_estep_io_result *res, int64_t P, void *ws,
-                            hipStream_t st);
 
 /* Tick -> zig-zag -> leg feature extractor (hhmm_features.hip). */
 size_t features_workspace_bytes(int64_t n);

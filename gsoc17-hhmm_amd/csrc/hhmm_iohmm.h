@@ -1078,7 +1078,7 @@ iohmm_sp_kernel(const DevArgs a)
 /* The state-parallel sweep's profile and range: K = 2..4, outputs within
  * loglik / alpha / gamma / FFBS, a batch that leaves lane-per-pair below two
  * waves per SIMD (HHMM_FLAG_VIT_LANES / _VIT_STATES force one layout). */
-static bool io_states(const DevArgs &a)
+static inline bool io_states(const DevArgs &a)
 {
     const uint32_t sp_out = HHMM_OUT_LOGLIK | HHMM_OUT_ALPHA | HHMM_OUT_GAMMA | HHMM_OUT_FFBS;
     if (a.K < 2 || a.K > 4 || (a.outputs & ~sp_out) || (a.flags & HHMM_FLAG_VIT_LANES))

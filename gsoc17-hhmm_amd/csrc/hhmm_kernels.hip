@@ -99,7 +99,7 @@ ScanPlan scan_plan(int model, int K, int Tmax, int64_t P, uint32_t outputs, uint
                         model == HHMM_MODEL_HMM_MULTINOM_SEMISUP || model == HHMM_MODEL_TAYAL;
     const uint32_t fb_out = HHMM_OUT_LOGLIK | HHMM_OUT_UNALPHA | HHMM_OUT_ALPHA | HHMM_OUT_UNBETA | HHMM_OUT_BETA |
                             HHMM_OUT_UNGAMMA | HHMM_OUT_GAMMA;
-    /* the log-scale outputs run the sequential log-space recursion (hhmm_hmm.h) */
+    /* the log-scale outputs run the sequential log-space recursion (hhmm_fblog.h) */
     if (!family || (flags & HHMM_FLAG_SCAN_OFF) ||
         (outputs & (HHMM_OUT_FFBS | HHMM_OUT_UNALPHA | HHMM_OUT_UNBETA)) || !(outputs & fb_out))
         return sp;

@@ -61,7 +61,7 @@ constexpr int kLRenorm = HHMM_LK_RENORM;
 static_assert(kLChunk % kLRenorm == 0, "checkpoint steps are renormalisation steps");
 /* The cadence is taken only where the pair's parameters bound the shrink:
  * b = phi_min * min(min_i rowmax_i(A), min_i colmax_i(A)) >= 2^-39 (the lane
- * kernels' renorm_sparse_safe argument, hhmm_hmm.h).  Gaussian emissions have
+ * kernels' renorm_sparse_safe argument, hhmm_fbchunk.h).  Gaussian emissions have
  * no such bound (a density ratio can be anything), and a wave holding an
  * unbounded pair renormalises every step. */
 constexpr double kLRenormSafeBound = 0x1p-39;

@@ -1,13 +1,13 @@
 /*
  * hhmm_vscan.h -- T-parallel exact Viterbi for batches of few pairs with long
  * series (SURVEY.md §8 A11 at the C5 shape: 250 pairs x T = 1e6 per GPU, the
- * HMM family at K = 2 and 4).  Included by hhmm_hmm.h; DESIGN.md §3.5.
+ * HMM family at K = 2 and 4).  DESIGN.md §3.5c.
  *
  * The reference's recursion (hhmm-tayal2009.stan:130-165, hmm.stan:104-117)
  *   delta_t(j) = max_i fl(fl(delta_{t-1}(i) + a) + b)
  * (a, b = log A(i, j) and log phi(j, x_t) in the model's order, strict '>'
  * from -inf) is sequential in t and its rounding depends on the magnitude of
- * delta, which grows like t.  The decoders of hhmm_hmm.h therefore walk T one
+ * delta, which grows like t.  The decoders of hhmm_viterbi.h therefore walk T one
  * step at a time; at C5 that leaves 16 waves on a 1024-SIMD chip.
  *
  * What makes T-parallel decoding exact: inside one binade [2^k, 2^(k+1)) of
@@ -50,7 +50,13 @@
  * chunk exits disagree is decoded sequentially.
  */
 #pragma once
+#include <stdio.h>
+
+#include <algorithm>
 #include <type_traits>
+#include <vector>
+
+#include "hhmm_viterbi.h"
 
 namespace hhmm {
 
@@ -1210,7 +1216,7 @@ __global__ void __launch_bounds__(64) vs_scan1_kernel(const DevArgs a)
 }
 
 /* Each chunk again from its exact entry in the reference's arithmetic:
- * back-pointer words (the layout of hhmm_hmm.h's decoders), the backtrack map
+ * back-pointer words (the layout of hhmm_viterbi.h's decoders), the backtrack map
  * and the bitwise check of the exit against the scan. */
 template <int MODEL, int K>
 __global__ void __launch_bounds__(kBlock) vs_replay_kernel(const DevArgs a)

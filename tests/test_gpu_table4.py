@@ -121,7 +121,7 @@ def test_table8_point_full_model(engine, oracle, pars):
 
 # ---- degenerate draws on the sign-class paths ------------------------------------
 # The Tayal kernels skip the flattened HHMM's structural transition zeros when a wave's lanes
-# share a step's sign (hhmm_hmm.h tayal_nz / tayal_dispatch).  0 x f adds nothing to a sum of
+# share a step's sign (hhmm_step.h tayal_nz / tayal_dispatch).  0 x f adds nothing to a sum of
 # finite terms, but the reference computes in log space, where a NaN on a skipped path still
 # reaches every accumulator (NaN + -inf = NaN, hhmm-tayal2009.stan:60-71).  The skip is taken
 # only where the wave's p_11, A_row and phi_k are all probabilities; these draws are not, and

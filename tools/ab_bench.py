@@ -5,7 +5,7 @@
   python tools/ab_bench.py NAME=path/to/libhhmm.so[@VAR=VAL,...] [NAME=...] [--rounds 5] [--pairs 1000000] [--T 1000]
 
 (@VAR=VAL sets environment variables around that variant's launches, e.g. the
-HHMM_PROBE_*_LDS_KB occupancy probes of hhmm_hmm.h)
+HHMM_PROBE_*_LDS_KB occupancy probes of the launch templates in hhmm_hmm.h)
 
 Each variant runs the bench.py C2 step (fb_kernel, then viterbi_kernel, then
 the two concurrently on two streams as bench.py does: "pair") on
