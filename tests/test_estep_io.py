@@ -12,7 +12,8 @@ unless stated, and the device entry (hhmm_estep_io_device on torch's stream).
 Shapes: M <= 4 and M > 4 are the kernel's two input classes (an odd M pads its
 class), K * MMAX > 32 moves gw from registers into the LDS slab (reg K = 5 at
 M = 5, 8; mix (5, 2, 5)), T = 1 has no transition and T = 2 exactly one, P
-covers the partial last wave.
+covers the partial last wave; T = 3000 is the long series of the sibling
+entries' files.  Batches past one workgroup: tests/test_stats_geometry.py.
 """
 import ctypes as C
 import pathlib
@@ -327,8 +328,11 @@ def test_m_step_nan_pair_gets_nan_parameters():
 
 # ---------------------------------------------------------------- GPU
 
-REG_SHAPES = [(K, M) for K in (1, 2, 3, 4, 5, 8) for M in (1, 2, 4, 5, 8) if M <= 4 or K <= 5]
-MIX_SHAPES = [(1, 1, 1), (2, 3, 4), (4, 3, 4), (5, 2, 5), (8, 3, 4), (4, 8, 8)]
+# every K and M inside the LDS fit BAD pins (M > 4 needs K <= 5); M = 3, 6 and 7 pad their MMAX class, K = 6 and 7
+# at M <= 4 are the 3- and 2-wave classes
+REG_SHAPES = [(K, M) for K in range(1, 9) for M in range(1, 9) if M <= 4 or K <= 5]
+MIX_SHAPES = [(1, 1, 1), (2, 3, 4), (4, 3, 4), (5, 2, 5), (8, 3, 4), (4, 8, 8),
+              (3, 2, 3), (6, 2, 3), (7, 2, 4), (2, 3, 6), (3, 2, 7), (4, 8, 7)]
 
 
 @pytest.mark.gpu
@@ -401,6 +405,20 @@ def test_gpu_ragged_lengths_inside_one_wave(engine, model, K, M, L):
     data["T"] = lens
     got, _want = check(engine, model, data, draws)
     assert all(np.isfinite(got[k]).all() for k in got if k not in ("status", "pair_status"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("model,K,M,L", [("iohmm-reg", 3, 4, 0), ("iohmm-mix", 3, 3, 2)])
+def test_gpu_long_series_keeps_its_scale(engine, model, K, M, L):
+    """T = 3000: exp(loglik) underflows fp64 (log of the smallest subnormal is -744.4).  Every step is in log
+    space on its own and the sums have 3000 terms of order one, so the parity tolerance holds as it stands."""
+    T = 3000
+    data, draws = make(model, 2, 2, T, K, M, L, seed=30)
+    got, _want = check(engine, model, data, draws)
+    assert (got["loglik"] < -745.0).all() and np.isfinite(got["loglik"]).all()
+    count = got["n_k"].sum(axis=1) if model == "iohmm-reg" else got["n_kl"].sum(axis=(1, 2))
+    assert np.max(np.abs(count - T)) <= TOL * T
+    assert np.allclose(got["gw_km"].sum(axis=1), 0.0, rtol=0, atol=TOL * T)
 
 
 @pytest.mark.gpu
