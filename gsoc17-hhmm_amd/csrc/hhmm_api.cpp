@@ -1742,8 +1742,9 @@ hhmm_status hhmm_extract_features(const hhmm_ticks *ticks, hhmm_legs *legs, int 
 /* ------------------------------------------------------------------ */
 /* Statistics per (series, draw) pair: the E-step (include/hhmm_estep.h), */
 /* the draw statistics (hhmm_gibbs.h, hhmm_gibbs_gauss.h), the expected  */
-/* draw statistics (hhmm_expect.h) and the IOHMM E-step                 */
-/* (hhmm_estep_io.h) share one host path                                */
+/* draw statistics (hhmm_expect.h), the IOHMM E-step (hhmm_estep_io.h)  */
+/* and the pointwise predictive densities (hhmm_pointwise.h) share one  */
+/* host path                                                            */
 /* ------------------------------------------------------------------ */
 
 /* One array of a host call: uploaded from host_in, or downloaded to host_out
@@ -1761,6 +1762,7 @@ struct StatsArr {
 union StatsResult {
     hhmm_estep_result estep;
     hhmm_estep_io_result io;
+    hhmm_pointwise_result pw;
 };
 
 /* What tells the entries apart on the host.  The result struct is the
@@ -1770,7 +1772,7 @@ struct StatsEntry {
     bool reads_u;     /* ffbs_u is an input (elsewhere the field is ignored) */
     hhmm_status (*check)(const hhmm_request *, const void *);
     hhmm_status (*launch)(const hhmm_request *, const void *, int64_t, void *, hipStream_t);
-    size_t (*workspace)(int K, int Tmax, int64_t P);
+    size_t (*workspace)(const hhmm_request *req, int64_t P);
     /* the arrays of a host call: req / res on the host, dr / dq their device-side copies */
     void (*arrays)(const StatsEntry &en, const hhmm_request *req, const void *res, hhmm_request *dr, StatsResult *dq,
                    std::vector<StatsArr> &arrs);
@@ -1865,32 +1867,75 @@ static void estep_io_arrays(const StatsEntry &, const hhmm_request *req, const v
     };
 }
 
-static size_t no_workspace(int, int, int64_t) { return 0; }
+/* hhmm_pointwise_result: the [N, T_max] reductions are N * T_max * 8 bytes; the
+ * per-step arrays are uploaded too, so that a step t >= T[n] comes back as the
+ * caller left it */
+static void pointwise_arrays(const StatsEntry &, const hhmm_request *req, const void *res_, hhmm_request *dr_,
+                             StatsResult *dq_, std::vector<StatsArr> &arrs)
+{
+    const hhmm_pointwise_result *res = (const hhmm_pointwise_result *)res_;
+    hhmm_request &dr = *dr_;
+    hhmm_pointwise_result &dq = dq_->pw;
+    const hhmm_data &d = req->data;
+    const hhmm_draws &w = req->draws;
+    const size_t N = (size_t)d.n_series, S = (size_t)w.n_draws, Tm = (size_t)d.T_max, K = (size_t)d.K;
+    const size_t P = (size_t)npairs(req);
+    const bool gauss = req->model == HHMM_MODEL_HMM_GAUSS; /* else hmm-multinom */
+    const size_t L = gauss ? 0 : (size_t)d.L;
+    arrs = {
+        {d.T, nullptr, (void **)&dr.data.T, N * 4},
+        {gauss ? nullptr : d.x_int, nullptr, (void **)&dr.data.x_int, N * Tm * 4},
+        {gauss ? d.x_real : nullptr, nullptr, (void **)&dr.data.x_real, N * Tm * 8},
+        {w.p_1k, nullptr, (void **)&dr.draws.p_1k, S * K * 8},
+        {w.A_ij, nullptr, (void **)&dr.draws.A_ij, S * K * K * 8},
+        {gauss ? nullptr : w.phi_k, nullptr, (void **)&dr.draws.phi_k, S * K * L * 8},
+        {gauss ? w.mu_k : nullptr, nullptr, (void **)&dr.draws.mu_k, S * K * 8},
+        {gauss ? w.sigma_k : nullptr, nullptr, (void **)&dr.draws.sigma_k, S * K * 8},
+        {nullptr, res->loglik, (void **)&dq.loglik, P * 8},
+        {res->lpd_t, res->lpd_t, (void **)&dq.lpd_t, N * Tm * 8},
+        {res->mean_t, res->mean_t, (void **)&dq.mean_t, N * Tm * 8},
+        {res->var_t, res->var_t, (void **)&dq.var_t, N * Tm * 8},
+        {res->lp_t, res->lp_t, (void **)&dq.lp_t, P * Tm * 8},
+        {nullptr, res->pair_status, (void **)&dq.pair_status, P * 4},
+    };
+}
+
+static size_t no_workspace(const hhmm_request *, int64_t) { return 0; }
+static size_t estep_workspace(const hhmm_request *req, int64_t P)
+{
+    return estep_workspace_bytes(req->data.K, req->data.T_max, P);
+}
 
 static const StatsEntry kEstep = {"E-step",
                                   false,
                                   typed_check<hhmm_estep_result, check_estep>,
                                   typed_launch<hhmm_estep_result, launch_estep>,
-                                  estep_workspace_bytes,
+                                  estep_workspace,
                                   estep_arrays};
 static const StatsEntry kDrawStats = {"draw statistics",
                                       true,
                                       typed_check<hhmm_estep_result, check_draw_stats>,
                                       typed_launch<hhmm_estep_result, launch_draw_stats>,
-                                      estep_workspace_bytes,
+                                      estep_workspace,
                                       estep_arrays};
 static const StatsEntry kDrawStatsGauss = {"Gaussian draw statistics",
                                            true,
                                            typed_check<hhmm_estep_result, check_draw_stats_gauss>,
                                            typed_launch<hhmm_estep_result, launch_draw_stats_gauss>,
-                                           estep_workspace_bytes,
+                                           estep_workspace,
                                            estep_arrays};
 static const StatsEntry kExpectedStats = {"expected statistics",
                                           false,
                                           typed_check<hhmm_estep_result, check_expected_stats>,
                                           typed_launch<hhmm_estep_result, launch_expected_stats>,
-                                          estep_workspace_bytes,
+                                          estep_workspace,
                                           estep_arrays};
+static const StatsEntry kPointwise = {"pointwise",
+                                      false,
+                                      typed_check<hhmm_pointwise_result, check_pointwise>,
+                                      typed_launch<hhmm_pointwise_result, launch_pointwise>,
+                                      pointwise_workspace_bytes,
+                                      pointwise_arrays};
 static const StatsEntry kEstepIo = {"IOHMM E-step",
                                     false,
                                     typed_check<hhmm_estep_io_result, check_estep_io>,
@@ -1930,7 +1975,7 @@ static hhmm_status stats_workspace_size(const StatsEntry &en, const hhmm_request
         set_error("%s: K = %d, the lane-per-pair kernel supports K <= %d", en.name, req->data.K, kMaxK);
         return HHMM_ERR_UNSUPPORTED;
     }
-    *bytes = en.workspace(req->data.K, req->data.T_max, P);
+    *bytes = en.workspace(req, P);
     return HHMM_OK;
 }
 
@@ -1943,7 +1988,7 @@ static hhmm_status stats_device(const StatsEntry &en, const hhmm_request *req, c
     if ((s = check_device()) != HHMM_OK)
         return s;
     const int64_t P = npairs(req);
-    const size_t need = en.workspace(req->data.K, req->data.T_max, P);
+    const size_t need = en.workspace(req, P);
     if (workspace_bytes_ < need || (need && !workspace)) {
         set_error("workspace of %zu bytes < %zu required", workspace_bytes_, need);
         return HHMM_ERR_INVALID_ARGUMENT;
@@ -1964,7 +2009,6 @@ static hhmm_status stats_host(const StatsEntry &en, const hhmm_request *req, con
     hipError_t e = hipSetDevice(dev);
     if (e != hipSuccess)
         return hip_fail(e, "hipSetDevice");
-    const hhmm_data &d = req->data;
     const size_t P = (size_t)npairs(req);
     hhmm_request dr = *req;
     StatsResult dq{};
@@ -1978,7 +2022,7 @@ static hhmm_status stats_host(const StatsEntry &en, const hhmm_request *req, con
         if ((a.host_in || a.host_out) && a.bytes)
             total += (a.bytes + 255) & ~(size_t)255;
     }
-    const size_t wsb = en.workspace(d.K, d.T_max, (int64_t)P);
+    const size_t wsb = en.workspace(req, (int64_t)P);
     char *blk = (char *)pool_get(dev, total);
     void *ws = pool_get(dev, wsb);
     auto cleanup = [&]() {
@@ -2082,6 +2126,20 @@ hhmm_status hhmm_estep_io_device(const hhmm_request *req, hhmm_estep_io_result *
 hhmm_status hhmm_estep_io(const hhmm_request *req, hhmm_estep_io_result *res)
 {
     return stats_host(kEstepIo, req, res);
+}
+
+hhmm_status hhmm_pointwise_workspace_size(const hhmm_request *req, size_t *bytes)
+{
+    return stats_workspace_size(kPointwise, req, bytes);
+}
+hhmm_status hhmm_pointwise_device(const hhmm_request *req, hhmm_pointwise_result *res, void *workspace,
+                                  size_t workspace_bytes_, void *stream)
+{
+    return stats_device(kPointwise, req, res, workspace, workspace_bytes_, stream);
+}
+hhmm_status hhmm_pointwise(const hhmm_request *req, hhmm_pointwise_result *res)
+{
+    return stats_host(kPointwise, req, res);
 }
 
 } // extern "C"

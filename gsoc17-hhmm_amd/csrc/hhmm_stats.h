@@ -2,11 +2,12 @@
  * hhmm_stats.h -- host-side pieces shared by the "statistics per (series,
  * draw) pair" entries: the E-step (hhmm_estep.hip), the draw statistics
  * (hhmm_draw_stats.hip, hhmm_draw_stats_gauss.hip), the expected draw
- * statistics (hhmm_expect.hip) and the IOHMM E-step (hhmm_estep_io.hip).  The
+ * statistics (hhmm_expect.hip), the IOHMM E-step (hhmm_estep_io.hip) and the
+ * pointwise predictive densities (hhmm_pointwise.hip).  The
  * kernels differ; the argument checks, the DevArgs of a launch, the LDS fit,
  * the dispatch on K and the launch epilogue do not.  stats_check_tail belongs
- * to the four entries that fill an hhmm_estep_result; the IOHMM E-step has a
- * result struct and a tail of its own.  Not part of the public ABI.
+ * to the four entries that fill an hhmm_estep_result; the IOHMM E-step and the
+ * pointwise densities have a result struct and a tail of their own.  Not part of the public ABI.
  */
 #pragma once
 #include <type_traits>
@@ -17,10 +18,11 @@
 #include "hhmm_gibbs.h"
 #include "hhmm_gibbs_gauss.h"
 #include "hhmm_internal.h"
+#include "hhmm_pointwise.h"
 
 namespace hhmm {
 
-/* Each of the five entries gives the host path of hhmm_api.cpp (StatsEntry,
+/* Each of the six entries gives the host path of hhmm_api.cpp (StatsEntry,
  * stats_*) a check_* and a launch_*; what those share follows them.
  *
  * Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
@@ -53,6 +55,15 @@ hhmm_status launch_expected_stats(const hhmm_request *r, const hhmm_estep_result
 hhmm_status check_estep_io(const hhmm_request *r, const hhmm_estep_io_result *o);
 hhmm_status launch_estep_io(const hhmm_request *r, const hhmm_estep_io_result *res, int64_t P, void *ws,
                             hipStream_t st);
+
+/* Pointwise predictive densities (hhmm_pointwise.hip): argument checks (no
+ * device needed), the tiles' partials (0 bytes while one workgroup covers a
+ * series' draws) and the launch on `st` (device pointers); its own result
+ * struct and tail. */
+hhmm_status check_pointwise(const hhmm_request *r, const hhmm_pointwise_result *o);
+size_t pointwise_workspace_bytes(const hhmm_request *r, int64_t P);
+hhmm_status launch_pointwise(const hhmm_request *r, const hhmm_pointwise_result *res, int64_t P, void *ws,
+                             hipStream_t st);
 
 /* Head of an entry's check_*, in this order: NULL request, ABI, model id, the
  * entry's scope (`scope` says which models it takes and where the others go),

@@ -15,6 +15,7 @@ from .estep import estep, m_step, score  # noqa: F401
 from .expect import expected_stats  # noqa: F401
 from .em import baum_welch  # noqa: F401
 from .estep_io import em_io, estep_io, m_step_io, score_io  # noqa: F401
+from .pointwise import pointwise_predictive, waic  # noqa: F401
 from .gibbs import conditional_draw, draw_stats, gibbs, stack_chains  # noqa: F401
 from .gibbs_gauss import conditional_draw_gauss, draw_stats_gauss, gibbs_gauss, relabel_ordered  # noqa: F401
 

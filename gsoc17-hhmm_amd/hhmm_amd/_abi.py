@@ -222,6 +222,18 @@ class EstepResult(C.Structure):
     ]
 
 
+# include/hhmm_pointwise.h
+class PointwiseResult(C.Structure):
+    _fields_ = [
+        ("loglik", C.c_void_p),
+        ("lpd_t", C.c_void_p),
+        ("mean_t", C.c_void_p),
+        ("var_t", C.c_void_p),
+        ("lp_t", C.c_void_p),
+        ("pair_status", C.c_void_p),
+    ]
+
+
 # include/hhmm_estep_io.h
 class EstepIoResult(C.Structure):
     _fields_ = [
@@ -373,4 +385,12 @@ def declare(lib):
     lib.hhmm_estep_io_device.restype = C.c_int
     lib.hhmm_estep_io.argtypes = [RP, IP]
     lib.hhmm_estep_io.restype = C.c_int
+    # include/hhmm_pointwise.h
+    WP = C.POINTER(PointwiseResult)
+    lib.hhmm_pointwise_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
+    lib.hhmm_pointwise_workspace_size.restype = C.c_int
+    lib.hhmm_pointwise_device.argtypes = [RP, WP, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.hhmm_pointwise_device.restype = C.c_int
+    lib.hhmm_pointwise.argtypes = [RP, WP]
+    lib.hhmm_pointwise.restype = C.c_int
     return lib
