@@ -220,30 +220,16 @@ static void pool_release_all()
 
 /* ---------------- request description ---------------- */
 
-static bool is_iohmm(int m)
-{
-    return m == HHMM_MODEL_IOHMM_REG || m == HHMM_MODEL_IOHMM_MIX || m == HHMM_MODEL_IOHMM_HMIX ||
-           m == HHMM_MODEL_IOHMM_HMIX_LITE;
-}
-static bool is_discrete(int m)
-{
-    return m == HHMM_MODEL_HMM_MULTINOM || m == HHMM_MODEL_HMM_MULTINOM_SEMISUP || m == HHMM_MODEL_TAYAL ||
-           m == HHMM_MODEL_TAYAL_LITE;
-}
-
-/* Outputs each Stan program declares (TP / GQ names), SURVEY.md §2.3. */
+/* Outputs each Stan program declares (TP / GQ names); the
+ * output classes and model predicates are hhmm_plan.h's. */
 static uint32_t available_outputs(int m)
 {
-    const uint32_t fb = HHMM_OUT_LOGLIK | HHMM_OUT_UNALPHA | HHMM_OUT_ALPHA | HHMM_OUT_UNBETA | HHMM_OUT_BETA |
-                        HHMM_OUT_UNGAMMA | HHMM_OUT_GAMMA | HHMM_OUT_ZSTAR | HHMM_OUT_LOGP_ZSTAR;
+    const uint32_t fb = kOutFb | kOutVit;
     /* FFBS (the engine's contract, §8 A14) is offered wherever the program has
      * a forward filter over the full series and a backward pass */
-    switch (m) {
-    case HHMM_MODEL_HMM_GAUSS:
-    case HHMM_MODEL_HMM_MULTINOM:
-    case HHMM_MODEL_HMM_MULTINOM_SEMISUP:
-    case HHMM_MODEL_TAYAL:
+    if (hmm_has_backward(m))
         return fb | HHMM_OUT_FFBS;
+    switch (m) {
     case HHMM_MODEL_IOHMM_REG:
     case HHMM_MODEL_IOHMM_MIX:
         /* + the fitted-output GQ draws (iohmm-reg.stan:124-148; iohmm-mix.stan:133-161) */
@@ -1296,6 +1282,15 @@ hhmm_status hhmm_workspace_size(const hhmm_request *req, size_t *bytes)
     return HHMM_OK;
 }
 
+hhmm_status hhmm_selftest_plan(const hhmm_request *req, char *buf, size_t n)
+{
+    if (!req || !buf || n == 0 || npairs(req) < 1) {
+        set_error("NULL argument, or a request that describes no pairs");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    return selftest_plan(req, npairs(req), buf, n);
+}
+
 hhmm_status hhmm_run_device(const hhmm_request *req, hhmm_result *res, void *workspace, size_t workspace_bytes_,
                             void *stream)
 {
@@ -1451,15 +1446,13 @@ static hhmm_status segment_check(const hhmm_request *req, const hhmm_segment *se
         return HHMM_ERR_INVALID_ARGUMENT;
     }
     const int m = req->model;
-    if (!(m == HHMM_MODEL_HMM_GAUSS || m == HHMM_MODEL_HMM_MULTINOM || m == HHMM_MODEL_HMM_MULTINOM_SEMISUP ||
-          m == HHMM_MODEL_TAYAL) ||
-        req->data.K > kMaxKLarge ||
+    if (!hmm_has_backward(m) || req->data.K > kMaxKLarge ||
         (req->data.K > kMaxK && m != HHMM_MODEL_HMM_MULTINOM && m != HHMM_MODEL_HMM_GAUSS)) {
         set_error("segment windows: the HMM family at K <= %d (hmm, hmm-multinom, semisup, tayal), "
                   "hmm and hmm-multinom at K <= %d", kMaxK, kMaxKLarge);
         return HHMM_ERR_UNSUPPORTED;
     }
-    const uint32_t ok = HHMM_OUT_LOGLIK | HHMM_OUT_ALPHA | HHMM_OUT_BETA | HHMM_OUT_UNGAMMA | HHMM_OUT_GAMMA;
+    const uint32_t ok = kOutFb & ~kOutLog;
     if (req->outputs & ~ok) {
         set_error("segment windows: outputs 0x%x have no segment form (loglik, alpha_tk, beta_tk, ungamma_tk, "
                   "gamma_tk only; the Viterbi and FFBS stay sequential per pair)", req->outputs & ~ok);

@@ -337,14 +337,6 @@ __device__ __forceinline__ int ffbs_cat(const double (&w)[K], double u)
     return ((sum > 0.0) & __builtin_isfinite(sum)) ? b : -1;
 }
 
-/* Viterbi chunk length: a multiple of the back-pointer steps per word so
- * that every word boundary falls on a static unrolled slot. */
-constexpr int vit_chunk(int K)
-{
-    return bp_steps_per_word(K) >= 8 ? bp_steps_per_word(K)
-                                      : (8 % bp_steps_per_word(K) == 0 ? 8 : 2 * bp_steps_per_word(K));
-}
-
 /* Backtrack over chunk c (descending): zb[u] = zstar[t0 + u] (1-based) for
  * the chunk's steps inside the series, stepping z; the stores are issued
  * later (vit_back_flush), after the next chunk's word loads, so that waiting

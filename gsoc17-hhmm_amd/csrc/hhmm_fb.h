@@ -19,7 +19,7 @@ namespace hhmm {
 template <int MODEL, int K>
 constexpr bool fb_big_ok()
 {
-    return MODEL == HHMM_MODEL_HMM_MULTINOM && fb_chunk(K) == 8;
+    return fb_big_ok(MODEL, K);
 }
 
 /* Observation u of a kBigChunk-step block from its packed words (FB_PACK). */

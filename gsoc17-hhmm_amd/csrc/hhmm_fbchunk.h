@@ -19,24 +19,7 @@ namespace hhmm {
 /* Forward / backward / posteriors                                       */
 /* ------------------------------------------------------------------ */
 
-/* Output profile of the forward-backward kernel (compile time). */
-enum FbMode {
-    FB_GAMMA = 0, /* loglik + gamma_tk: the hot path, no per-output branches */
-    FB_FULL = 1,  /* any mix of alpha/beta/unalpha/unbeta/ungamma/gamma (+ per-step log scale) */
-    FB_FWD = 2,   /* forward only: loglik / alpha / unalpha (tayal-lite, no backward output) */
-    FB_FFBS = 4,  /* flag: FFBS draws in the backward sweep */
-    FB_PACK = 8,  /* flag: the forward sweep packs each chunk's symbols (4 bits, L <= 16)
-                   * into the checkpoint record; the backward sweep reads those
-                   * instead of re-reading x (hmm-multinom: 4 B -> 1 B per step) */
-    FB_BIG = 16,  /* flag (gamma profile): checkpoints every kBigChunk steps, and a
-                   * two-level recompute in the backward sweep (every kGroup-th
-                   * state kept, each group recomputed before it is consumed):
-                   * checkpoint traffic 8 -> 4 B per step for ~1.44 forward
-                   * recomputes per step instead of 1 */
-    FB_RN1 = 32   /* flag (with FB_BIG): renormalise every step -- the waves whose
-                   * pairs' parameters do not bound the kBigRenorm-step shrink
-                   * (renorm_sparse_safe) */
-};
+/* FbMode, the output profile of the forward-backward kernel (compile time): hhmm_plan.h */
 constexpr int fb_base(int mode) { return mode & 3; }
 constexpr bool fb_ffbs(int mode) { return (mode & FB_FFBS) != 0; }
 constexpr bool fb_pack(int mode) { return (mode & FB_PACK) != 0; }

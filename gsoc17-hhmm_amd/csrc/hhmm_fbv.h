@@ -32,7 +32,7 @@ namespace hhmm {
 template <int MODEL, int K>
 constexpr bool fbv_ok()
 {
-    return fb_big_ok<MODEL, K>() && vit_chunk(K) == fb_chunk(K);
+    return fbv_ok(MODEL, K);
 }
 
 /* FB_BIG backward sweep and the Viterbi backtrack over the same kBigChunk-step
@@ -263,9 +263,6 @@ __global__ void __launch_bounds__(kBlock) fbv_kernel(const DevArgs a)
  * are bit-identical to the two kernels (same functions, same operation order).
  * A wave holding a pair without the renormalisation bound lists itself after
  * phase 1 (zstar_T parked in zstar[T-1]) for vfb_dense_kernel. */
-#ifndef HHMM_VFB_DEFAULT
-#define HHMM_VFB_DEFAULT 1 /* the phased sweep for the C2 request without flags */
-#endif
 template <int MODEL, int K>
 __device__ __forceinline__ uint32_t pack_chunk(const Obs (&cur)[8])
 {

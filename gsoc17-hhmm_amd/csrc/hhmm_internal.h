@@ -10,6 +10,7 @@
 
 #include "hhmm.h"
 #include "hhmm_features.h"
+#include "hhmm_plan.h"
 #include "hhmm_summary.h"
 
 namespace hhmm {
@@ -103,38 +104,13 @@ struct DevArgs {
     const double *seg_leave;/* [K + 1][P] */
 };
 
-/* Phase-3 lanes of the T-scan per T-chunk: P rounded up to whole waves. */
-constexpr int64_t scan_lanes_per_chunk(int64_t P) { return (P + 63) & ~(int64_t)63; }
+/* The WsRegion bits (hhmm_plan.h) whose workspace pointers are bound. */
+inline uint32_t bound_regions(const DevArgs &a)
+{
+    return (a.ckpt ? WS_CKPT : 0u) | (a.ckpt_ls ? WS_CKPT_LS : 0u) | (a.xpk ? WS_XPK : 0u) | (a.rnw ? WS_RNW : 0u) |
+           (a.bp ? WS_BP : 0u) | (a.sc_mf ? WS_SCAN : 0u) | (a.vs_m ? WS_VSCAN : 0u);
+}
 
-/* Parallel-scan plan of one request: T-chunk length and count (cl = 0: off). */
-struct ScanPlan {
-    int cl;
-    int nc;
-};
-ScanPlan scan_plan(int model, int K, int Tmax, int64_t P, uint32_t outputs, uint32_t flags);
-
-/* T-parallel exact Viterbi (hhmm_vscan.h): V-chunks of kVsChunk steps (a whole
- * number of back-pointer words at K = 2 and 4); returns the chunk count per
- * pair of a Viterbi over Tv steps, 0 when the sequential decoders run. */
-#ifndef HHMM_VS_CHUNK
-#define HHMM_VS_CHUNK 512 /* build knob: steps per V-chunk */
-#endif
-constexpr int kVsChunk = HHMM_VS_CHUNK;
-int vscan_chunks(int model, int K, int Tv, int64_t P, uint32_t outputs, uint32_t flags);
-
-/* Large K under GRID pairing (hhmm_lkscan.h lkm_fb_kernel): the k-steps of
- * its state capacity when it runs the forward-backward, else 0. */
-int lkm_plan(int model, int K, int64_t N, int pairing, uint32_t outputs, uint32_t flags, int scan_cl);
-
-/* Time steps between forward checkpoints kept for the backward sweep. */
-constexpr int fb_chunk(int K) { return K <= 4 ? 8 : 4; }
-
-/* Viterbi back-pointer packing: bits per state, bits per step, steps per word. */
-constexpr int bp_bits(int K) { return K <= 2 ? 1 : (K <= 4 ? 2 : (K <= 8 ? 3 : 4)); }
-constexpr int bp_steps_per_word(int K) { return 32 / (K * bp_bits(K)); }
-
-constexpr int kMaxK = 8;       /* lane-per-pair kernels (hhmm_hmm.h, hhmm_iohmm.h) */
-constexpr int kMaxKLarge = 32; /* state-parallel HMM-family kernels (hhmm_large.h) */
 constexpr int kBlock = 256;
 constexpr size_t kLdsLimit = 160 * 1024;
 
@@ -142,8 +118,11 @@ constexpr size_t kLdsLimit = 160 * 1024;
 size_t workspace_bytes(int model, int K, int L, int Tmax, int Toos, int64_t P, uint32_t outputs, uint32_t flags,
                        int64_t N, int pairing);
 
-/* Carves the workspace into DevArgs pointers. */
-void bind_workspace(DevArgs &a, void *ws, int Tmax, int Toos, uint32_t flags);
+/* Carves the workspace into DevArgs pointers; returns the request's launch
+ * plan (a.seg_phase set beforehand for a segment window). */
+HmmPlan bind_workspace(DevArgs &a, void *ws, int Tmax, int Toos, uint32_t flags);
+/* hhmm_selftest_plan: the plan and the regions bind_workspace binds, as one line. */
+hhmm_status selftest_plan(const hhmm_request *req, int64_t P, char *buf, size_t n);
 
 /* Launches every kernel the request needs on `stream` (device pointers).
  * check_data: the data arrays were not validated on the host (the device
@@ -151,19 +130,12 @@ void bind_workspace(DevArgs &a, void *ws, int Tmax, int Toos, uint32_t flags);
  * (HHMM_PAIR_INVALID_DATA) after the model's kernels. */
 hhmm_status launch_all(const hhmm_request *req, const hhmm_result *res, int64_t P, void *ws, hipStream_t st,
                        const hhmm_segment *seg = nullptr, int seg_phase = 0, bool check_data = false);
-/* Set by a launcher whose kernel checks the data-block constraints inline
- * (the phased sweep, launch_vfb): launch_all then skips its separate pass. */
-extern thread_local bool t_data_checked_inline;
 
 /* HMM family, one translation unit per model / K range (hhmm_m_*.hip). */
-hhmm_status run_gauss_lo(const DevArgs &a, const hhmm_request *req, const hhmm_result *res, hipStream_t st);
-hhmm_status run_gauss_hi(const DevArgs &a, const hhmm_request *req, const hhmm_result *res, hipStream_t st);
-hhmm_status run_multinom_lo(const DevArgs &a, const hhmm_request *req, const hhmm_result *res, hipStream_t st);
-hhmm_status run_multinom_hi(const DevArgs &a, const hhmm_request *req, const hhmm_result *res, hipStream_t st);
-hhmm_status run_semisup_lo(const DevArgs &a, const hhmm_request *req, const hhmm_result *res, hipStream_t st);
-hhmm_status run_semisup_hi(const DevArgs &a, const hhmm_request *req, const hhmm_result *res, hipStream_t st);
-hhmm_status run_tayal(const DevArgs &a, const hhmm_request *req, const hhmm_result *res, hipStream_t st);
-hhmm_status run_tayal_lite(const DevArgs &a, const hhmm_request *req, const hhmm_result *res, hipStream_t st);
+typedef hhmm_status RunModel(const DevArgs &a, const HmmPlan &plan, const hhmm_request *req, const hhmm_result *res,
+                             hipStream_t st);
+RunModel run_gauss_lo, run_gauss_hi, run_multinom_lo, run_multinom_hi, run_semisup_lo, run_semisup_hi, run_tayal,
+    run_tayal_lite;
 /* hmm / hmm-multinom at kMaxK < K <= kMaxKLarge (hhmm_m_large.hip) */
 hhmm_status run_large(const DevArgs &a, hipStream_t st);
 /* the IOHMM programs at kMaxK < K <= kMaxKLarge (hhmm_io_large.hip) */
@@ -171,12 +143,8 @@ hhmm_status run_large_iohmm(const DevArgs &a, hipStream_t st);
 
 /* IOHMM family (iohmm-reg / -mix / -hmix / -hmix-lite), hhmm_iohmm.hip. */
 hhmm_status launch_iohmm(const DevArgs &a, hipStream_t stream);
-/* The outputs the IOHMM linear-space filter produces; a pair whose filter
- * drops below kIoWeak is listed in a.io_redo and re-run in log space by
- * launch_iohmm_log (hhmm_iolog.hip). */
-constexpr uint32_t kIoFilt = HHMM_OUT_LOGLIK | HHMM_OUT_UNALPHA | HHMM_OUT_ALPHA | HHMM_OUT_UNBETA | HHMM_OUT_BETA |
-                             HHMM_OUT_UNGAMMA | HHMM_OUT_GAMMA | HHMM_OUT_OBLIK_T;
-constexpr uint32_t kIoBack = HHMM_OUT_UNBETA | HHMM_OUT_BETA | HHMM_OUT_UNGAMMA | HHMM_OUT_GAMMA;
+/* kIoFilt / kIoBack (hhmm_plan.h): a pair whose linear-space filter drops below
+ * kIoWeak is listed in a.io_redo and re-run in log space by launch_iohmm_log. */
 constexpr double kIoWeak = 0x1p-960;
 /* t = 0: f_0 = p .* e_0 keeps every component above 2^-1074, i.e. down to
  * 2^-834 (below the 1e-250 tolerance floor) of a max of at least 2^-240 */
@@ -209,6 +177,34 @@ hhmm_status join_stream(hipStream_t st, hipStream_t side);
 hhmm_status selftest_cr_math(const double *in, double *out, int64_t n, int which);
 
 void set_error(const char *fmt, ...);
+
+/* Waves per workgroup, at most kBlock / 64, whose tables of per_wave bytes
+ * each fit in LDS together (0: not even one), and the workgroup's LDS. */
+inline int waves_that_fit(size_t per_wave, size_t *lds, int waves = kBlock / 64)
+{
+    while (waves > 0 && per_wave * waves > kLdsLimit)
+        --waves;
+    *lds = per_wave * waves;
+    return waves;
+}
+
+/* The lane-per-pair kernels' emission table of K * L entries per wave exceeds LDS. */
+inline hhmm_status lds_fit_error(int K, int L)
+{
+    set_error("emission table K*L = %d*%d does not fit in LDS", K, L);
+    return HHMM_ERR_UNSUPPORTED;
+}
+
+/* After a launch: the launch error of `kernel`, if any. */
+inline hhmm_status launch_status(const char *kernel)
+{
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error("%s launch: %s", kernel, hipGetErrorString(e));
+        return HHMM_ERR_HIP;
+    }
+    return HHMM_OK;
+}
 
 /* Reduction over draws (hhmm_summary.hip): argument checks (no device needed)
  * and the launch on `st` (device pointers). */

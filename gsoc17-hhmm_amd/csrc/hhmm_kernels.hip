@@ -66,20 +66,6 @@ __global__ void cr_math_kernel(const double *in, double *out, int64_t n, int whi
 /* ------------------------------------------------------------------ */
 
 
-static bool needs_ckpt(int model, uint32_t out)
-{
-    const bool hmm_bwd = model == HHMM_MODEL_HMM_GAUSS || model == HHMM_MODEL_HMM_MULTINOM ||
-                         model == HHMM_MODEL_HMM_MULTINOM_SEMISUP || model == HHMM_MODEL_TAYAL;
-    return hmm_bwd &&
-           (out & (HHMM_OUT_UNBETA | HHMM_OUT_BETA | HHMM_OUT_UNGAMMA | HHMM_OUT_GAMMA | HHMM_OUT_FFBS)) != 0;
-}
-
-static bool is_iohmm_model(int model)
-{
-    return model == HHMM_MODEL_IOHMM_REG || model == HHMM_MODEL_IOHMM_MIX || model == HHMM_MODEL_IOHMM_HMIX ||
-           model == HHMM_MODEL_IOHMM_HMIX_LITE;
-}
-
 static int nchunk_of(int K, int T) { return (T + fb_chunk(K) - 1) / fb_chunk(K); }
 static int nword_of(int K, int T) { return T / bp_steps_per_word(K) + 1; }
 
@@ -89,131 +75,22 @@ static bool large_k(int K) { return K > kMaxK; }
 
 static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
-/* Parallel scan over T for the HMM-family forward-backward:
- * used when a batch has too few pairs to fill the chip with one lane per
- * pair.  The T-chunk length targets ~512k (pair, chunk) lanes. */
-ScanPlan scan_plan(int model, int K, int Tmax, int64_t P, uint32_t outputs, uint32_t flags)
-{
-    ScanPlan sp{0, 0};
-    const bool family = model == HHMM_MODEL_HMM_GAUSS || model == HHMM_MODEL_HMM_MULTINOM ||
-                        model == HHMM_MODEL_HMM_MULTINOM_SEMISUP || model == HHMM_MODEL_TAYAL;
-    const uint32_t fb_out = HHMM_OUT_LOGLIK | HHMM_OUT_UNALPHA | HHMM_OUT_ALPHA | HHMM_OUT_UNBETA | HHMM_OUT_BETA |
-                            HHMM_OUT_UNGAMMA | HHMM_OUT_GAMMA;
-    /* the log-scale outputs run the sequential log-space recursion (hhmm_fblog.h) */
-    if (!family || (flags & HHMM_FLAG_SCAN_OFF) ||
-        (outputs & (HHMM_OUT_FFBS | HHMM_OUT_UNALPHA | HHMM_OUT_UNBETA)) || !(outputs & fb_out))
-        return sp;
-    const int log2cl = (int)((flags >> 8) & 0xffu);
-    if (K > kMaxK) {
-        /* large K (hhmm_lkscan.h): hmm-multinom and hmm; chunks a multiple of the
-         * 32-step observation blocks; automatic when the batch is under 4096
-         * pairs (2048 waves of two groups: two per SIMD) and long, with about
-         * 128k (pair, chunk) groups for the chunks' sweeps.  At N2 (250 pairs x
-         * T = 10^6) that is 2048-step chunks: 223.4 ms against 228.2 for 4096
-         * and 226.0 for 1024, and lk_fb_kernel writes 55.7 GB against 68.1
-         * (1024: 53.6) for 46 GB of gamma + 5.75 GB of checkpoints: a 128-byte
-         * line of a gamma row is written by several waves, whose stores meet in
-         * L2 less often the longer the chunks (profiles/r04r_n2_chunks.txt) */
-        if ((model != HHMM_MODEL_HMM_MULTINOM && model != HHMM_MODEL_HMM_GAUSS) || K > kMaxKLarge)
-            return sp;
-        if (!(flags & HHMM_FLAG_SCAN_FORCE) && !(P < 4096 && Tmax >= 8192))
-            return sp;
-        int cl = 256;
-        if (log2cl > 0) {
-            cl = max(32, 1 << log2cl);
-        } else {
-            while ((int64_t)P * ((Tmax + cl - 1) / cl) > 131072 && cl < (1 << 20))
-                cl *= 2;
-        }
-        cl = (cl + 31) & ~31;
-        sp.cl = cl;
-        sp.nc = (Tmax + cl - 1) / cl;
-        return sp;
-    }
-    const int C = fb_chunk(K);
-    /* a batch of under 16384 pairs (256 waves: a quarter of the chip's SIMDs)
-     * is latency-bound on its T sequential steps already at T of a few hundred:
-     * chunks of 4 C steps (C1, 1000 pairs x T = 500: 0.32 -> 0.10 ms), grown
-     * until about 512k (pair, chunk) lanes.  At C5 (250 pairs x T = 10^6, the
-     * V-scan on the high-priority side stream) that is 512-step chunks: once
-     * the V-scan's tie chunks left its grid pass (round 6) the forward-backward
-     * chain was the longer one, and 512 measured 6.85 / 7.50 ms against 7.96 /
-     * 7.94 for 128, 7.19 for 256, 8.18 for 1024 (two boxes,
-     * profiles/r06w_ab_c5_fb_chunks*.log).  Before it, 128 had been best
-     * (9.80 ms against 10.22 for 256, profiles/r04l_ab_c5_rn4_chunks.log). */
-    const bool small = P < 16384 && Tmax >= 256;
-    int cl;
-    if (log2cl > 0) {
-        cl = 1 << log2cl;
-    } else if (small) {
-        cl = 4 * C;
-        while ((int64_t)P * ((Tmax + cl - 1) / cl) > 524288 && cl < 65536)
-            cl *= 2;
-    } else {
-        const int64_t want = (int64_t)Tmax * P / 524288;
-        cl = 8 * C;
-        while (cl < want && cl < 65536)
-            cl *= 2;
-    }
-    if (cl < C)
-        cl = C;
-    cl -= cl % C;
-    const int nc = (Tmax + cl - 1) / cl;
-    if (!(flags & HHMM_FLAG_SCAN_FORCE) && !small && (P >= 131072 || Tmax < 16384 || nc < 4))
-        return sp;
-    if (!(flags & HHMM_FLAG_SCAN_FORCE) && nc < 4)
-        return sp;
-    if (scan_lanes_per_chunk(P) * nc >= (int64_t(1) << 29)) /* checkpoint columns are 32-bit byte offsets */
-        return sp;
-    sp.cl = cl;
-    sp.nc = nc;
-    return sp;
-}
-
-int lkm_plan(int model, int K, int64_t N, int pairing, uint32_t outputs, uint32_t flags, int scan_cl)
-{
-    const uint32_t fb = HHMM_OUT_LOGLIK | HHMM_OUT_UNALPHA | HHMM_OUT_ALPHA | HHMM_OUT_UNBETA | HHMM_OUT_BETA |
-                        HHMM_OUT_UNGAMMA | HHMM_OUT_GAMMA;
-    if (model != HHMM_MODEL_HMM_MULTINOM || K <= kMaxK || K > kMaxKLarge || pairing != HHMM_PAIR_GRID || N < 16 ||
-        scan_cl > 0 || !(flags & HHMM_FLAG_LKM_MFMA) || !(outputs & fb) ||
-        (outputs & fb & ~(HHMM_OUT_LOGLIK | HHMM_OUT_GAMMA)))
-        return 0;
-    return K <= 16 ? 4 : (K <= 24 ? 6 : 8);
-}
-
-int vscan_chunks(int model, int K, int Tv, int64_t P, uint32_t outputs, uint32_t flags)
-{
-    const bool family = model == HHMM_MODEL_HMM_GAUSS || model == HHMM_MODEL_HMM_MULTINOM ||
-                        model == HHMM_MODEL_HMM_MULTINOM_SEMISUP || model == HHMM_MODEL_TAYAL ||
-                        model == HHMM_MODEL_TAYAL_LITE;
-    if (!family || !(K == 2 || K == 4) || !(outputs & (HHMM_OUT_ZSTAR | HHMM_OUT_LOGP_ZSTAR)) ||
-        (flags & (HHMM_FLAG_VIT_SCAN_OFF | HHMM_FLAG_VIT_LANES | HHMM_FLAG_VIT_STATES)))
-        return 0;
-    if (!(flags & HHMM_FLAG_VIT_SCAN) && (P >= 2048 || Tv < 16384))
-        return 0;
-    const int64_t nc = (Tv + kVsChunk - 1) / kVsChunk;
-    if (nc * P * K * K >= (int64_t(1) << 31)) /* 32-bit element offsets of the chunk products */
-        return 0;
-    return (int)nc;
-}
-
 /* Offsets of every workspace region (SIZE_MAX = unused) and the total. */
 struct WsLayout {
     size_t ckpt, ckpt_ls, xpk, rnw, bp, lam, ior, mf, qb, mx, st, sl, be, bl, total;
     size_t vm, vm1, vd, vk, ve, vz, vf, vt;
     size_t dc; /* [N] int32 data-check flags (the device entry) */
-    int vnc;
     ScanPlan sp;
+    HmmPlan plan; /* K <= kMaxK, HMM family: what is sized here is what run_model_k launches */
 };
 
 static WsLayout ws_layout(int model, int K, int L, int Tmax, int Toos, int64_t P, uint32_t outputs, uint32_t flags,
-                          int64_t N, int pairing)
+                          int64_t N, int pairing, int seg_phase = 0)
 {
     WsLayout w;
     const size_t NONE = SIZE_MAX;
     w.ckpt = w.ckpt_ls = w.xpk = w.rnw = w.bp = w.lam = w.ior = w.mf = w.qb = w.mx = w.st = w.sl = w.be = w.bl = NONE;
     w.vm = w.vm1 = w.vd = w.vk = w.ve = w.vz = w.vf = w.vt = NONE;
-    w.vnc = 0;
     w.dc = NONE;
     size_t off = 0;
     auto take = [&](size_t bytes) {
@@ -222,7 +99,8 @@ static WsLayout ws_layout(int model, int K, int L, int Tmax, int Toos, int64_t P
         return o;
     };
     const size_t d = sizeof(double);
-    w.sp = scan_plan(model, K, Tmax, P, outputs, flags);
+    w.plan = hmm_plan(model, K, L, Tmax, Toos, P, N, pairing, outputs, flags, seg_phase);
+    w.sp = large_k(K) ? scan_plan(model, K, Tmax, P, outputs, flags) : w.plan.sp;
     if (large_k(K)) {
         if (w.sp.cl > 0) {
             /* hhmm_lkscan.h: chunk products [P][nc][K][K] and row exponents
@@ -235,31 +113,31 @@ static WsLayout ws_layout(int model, int K, int L, int Tmax, int Toos, int64_t P
             w.sl = take(Q * d);
             w.be = take(Q * K * d);
             w.bl = take(Q * d); /* hmm.stan: each chunk's Gaussian log scale */
-            if (needs_ckpt(model, outputs))
+            if (needs_backward(model, outputs))
                 w.ckpt = take((size_t)((w.sp.cl + 7) / 8) * K * Q * d);
-        } else if (lkm_plan(model, K, N, pairing, outputs, flags, 0) && needs_ckpt(model, outputs)) {
+        } else if (lkm_plan(model, K, N, pairing, outputs, flags, 0) && needs_backward(model, outputs)) {
             /* lkm_fb_kernel: [wave][chunk][KSM][64] per (draw, 16-series tile) */
             const size_t ksm = (size_t)lkm_plan(model, K, N, pairing, outputs, flags, 0);
             w.ckpt = take((size_t)(P / N) * (size_t)((N + 15) / 16) * ((Tmax + 7) / 8) * ksm * 64 * d);
-        } else if (needs_ckpt(model, outputs)) {
+        } else if (needs_backward(model, outputs)) {
             w.ckpt = take((size_t)((Tmax + 7) / 8) * K * P * d);
         }
-        if (outputs & (HHMM_OUT_ZSTAR | HHMM_OUT_LOGP_ZSTAR))
+        if (outputs & kOutVit)
             w.bp = take((size_t)P * K * (size_t)((Tmax + 15) & ~15));
-        if (is_iohmm_model(model) && (outputs & HHMM_OUT_UNBETA))
-            w.lam = take((size_t)Tmax * P * d);
-        if (is_iohmm_model(model) && (outputs & kIoFilt))
-            w.ior = take((size_t)(1 + P) * sizeof(int32_t));
-        w.dc = take((size_t)N * sizeof(int32_t));
-        w.total = off + 256;
-        return w;
     }
-    if (w.sp.cl > 0) {
-        /* phase-3 checkpoint columns: one per (pair rounded up to whole waves, chunk) */
-        const size_t nc = (size_t)w.sp.nc, G = (size_t)scan_lanes_per_chunk(P) * nc,
-                     rows = (size_t)(w.sp.cl / fb_chunk(K));
-        w.ckpt = take(rows * K * G * d);
-        w.ckpt_ls = take(rows * G * d);
+    /* K <= kMaxK: exactly the regions the HMM family's plan names (the IOHMM
+     * programs: the back-pointers of their Viterbi) */
+    const uint32_t need = large_k(K) ? 0u : is_hmm_family(model) ? w.plan.regions : (outputs & kOutVit) ? WS_BP : 0u;
+    /* checkpoint records: one per (chunk, pair), or under the T-scan one per
+     * (chunk of a T-chunk, phase-3 column: pair rounded up to whole waves, T-chunk) */
+    const size_t nc = (size_t)w.sp.nc,
+                 rows = (need & WS_SCAN) ? (size_t)(w.sp.cl / fb_chunk(K)) : (size_t)nchunk_of(K, Tmax),
+                 cols = (need & WS_SCAN) ? (size_t)scan_lanes_per_chunk(P) * nc : (size_t)P;
+    if (need & WS_CKPT)
+        w.ckpt = take(rows * K * cols * d);
+    if (need & WS_CKPT_LS)
+        w.ckpt_ls = take(rows * cols * d);
+    if (need & WS_SCAN) {
         w.mf = take(nc * K * K * P * d);
         w.qb = take(nc * K * K * P * d);
         w.mx = take(nc * 3 * P * d);
@@ -267,38 +145,29 @@ static WsLayout ws_layout(int model, int K, int L, int Tmax, int Toos, int64_t P
         w.sl = take(nc * P * d);
         w.be = take(nc * K * P * d);
         w.bl = take(nc * P * d);
-    } else if (needs_ckpt(model, outputs)) {
-        w.ckpt = take((size_t)nchunk_of(K, Tmax) * K * P * d);
-        w.ckpt_ls = take((size_t)nchunk_of(K, Tmax) * P * d);
-        /* hot profile of hmm-multinom: symbols repacked 4 bits each for the backward sweep */
-        const uint32_t extra = HHMM_OUT_ALPHA | HHMM_OUT_UNALPHA | HHMM_OUT_BETA | HHMM_OUT_UNBETA | HHMM_OUT_UNGAMMA;
-        if (model == HHMM_MODEL_HMM_MULTINOM && L <= 16 && !(outputs & extra))
-            /* ceil(T/8) words (8-step chunks, 1 word each) or ceil(T/32) * 4
-             * (32-step chunks of the two-level recompute): at most T/8 + 4 */
-        {
-            w.xpk = take(((size_t)nchunk_of(K, Tmax) + 4) * P * sizeof(uint32_t));
-            w.rnw = take(((size_t)P / 64 + 64) * sizeof(int32_t)); /* one flag per fb_kernel wave */
-        }
     }
-    if (outputs & (HHMM_OUT_ZSTAR | HHMM_OUT_LOGP_ZSTAR)) {
-        const int Tv = (model == HHMM_MODEL_TAYAL_LITE) ? Toos : Tmax;
-        w.bp = take((size_t)nword_of(K, Tv) * P * sizeof(uint32_t));
-        w.vnc = vscan_chunks(model, K, Tv, P, outputs, flags);
-        if (w.vnc > 0) {
-            const size_t nc = (size_t)w.vnc;
-            w.vm = take(nc * K * K * P * d);
-            w.vm1 = take(nc * K * K * P * d);
-            w.vd = take((nc + 1) * K * P * d);
-            w.vk = take(nc * P * sizeof(int32_t));
-            w.ve = take(nc * P * sizeof(uint32_t));
-            w.vz = take(nc * P * sizeof(int32_t));
-            w.vf = take(P * sizeof(int32_t));
-            w.vt = take((1 + nc * P) * sizeof(int32_t));
-        }
+    /* packed symbols: ceil(T/8) words (8-step chunks, 1 word each) or
+     * ceil(T/32) * 4 (32-step chunks of the two-level recompute): at most T/8 + 4 */
+    if (need & WS_XPK)
+        w.xpk = take((rows + 4) * P * sizeof(uint32_t));
+    if (need & WS_RNW)
+        w.rnw = take(((size_t)P / 64 + 64) * sizeof(int32_t)); /* one flag per fb_kernel wave */
+    if (need & WS_BP)
+        w.bp = take((size_t)nword_of(K, model == HHMM_MODEL_TAYAL_LITE ? Toos : Tmax) * P * sizeof(uint32_t));
+    if (need & WS_VSCAN) {
+        const size_t vc = (size_t)w.plan.vs_nc;
+        w.vm = take(vc * K * K * P * d);
+        w.vm1 = take(vc * K * K * P * d);
+        w.vd = take((vc + 1) * K * P * d);
+        w.vk = take(vc * P * sizeof(int32_t));
+        w.ve = take(vc * P * sizeof(uint32_t));
+        w.vz = take(vc * P * sizeof(int32_t));
+        w.vf = take(P * sizeof(int32_t));
+        w.vt = take((1 + vc * P) * sizeof(int32_t));
     }
-    if (is_iohmm_model(model) && (outputs & HHMM_OUT_UNBETA))
+    if (is_iohmm(model) && (outputs & HHMM_OUT_UNBETA))
         w.lam = take((size_t)Tmax * P * d);
-    if (is_iohmm_model(model) && (outputs & kIoFilt))
+    if (is_iohmm(model) && (outputs & kIoFilt))
         w.ior = take((size_t)(1 + P) * sizeof(int32_t));
     w.dc = take((size_t)N * sizeof(int32_t));
     w.total = off + 256;
@@ -311,10 +180,10 @@ size_t workspace_bytes(int model, int K, int L, int Tmax, int Toos, int64_t P, u
     return ws_layout(model, K, L, Tmax, Toos, P, outputs, flags, N, pairing).total;
 }
 
-void bind_workspace(DevArgs &a, void *ws, int Tmax, int Toos, uint32_t flags)
+HmmPlan bind_workspace(DevArgs &a, void *ws, int Tmax, int Toos, uint32_t flags)
 {
     char *b = (char *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    const WsLayout w = ws_layout(a.model, a.K, a.L, Tmax, Toos, a.P, a.outputs, flags, a.N, a.pairing);
+    const WsLayout w = ws_layout(a.model, a.K, a.L, Tmax, Toos, a.P, a.outputs, flags, a.N, a.pairing, a.seg_phase);
     auto at_off = [&](size_t o) -> void * { return o == SIZE_MAX ? nullptr : (void *)(b + o); };
     a.ckpt = (double *)at_off(w.ckpt);
     a.ckpt_ls = (double *)at_off(w.ckpt_ls);
@@ -332,7 +201,7 @@ void bind_workspace(DevArgs &a, void *ws, int Tmax, int Toos, uint32_t flags)
     a.sc_sl = (double *)at_off(w.sl);
     a.sc_be = (double *)at_off(w.be);
     a.sc_bl = (double *)at_off(w.bl);
-    a.vs_nc = w.vnc;
+    a.vs_nc = w.plan.vs_nc;
     a.vs_m = (double *)at_off(w.vm);
     a.vs_m1 = (double *)at_off(w.vm1);
     a.vs_d = (double *)at_off(w.vd);
@@ -342,6 +211,7 @@ void bind_workspace(DevArgs &a, void *ws, int Tmax, int Toos, uint32_t flags)
     a.vs_fail = (int32_t *)at_off(w.vf);
     a.vs_tl = (int32_t *)at_off(w.vt);
     a.dc_flag = (int32_t *)at_off(w.dc);
+    return w.plan;
 }
 
 DevArgs make_args(const hhmm_request *req, const hhmm_result *res, int64_t P)
@@ -407,8 +277,6 @@ DevArgs make_args(const hhmm_request *req, const hhmm_result *res, int64_t P)
 /* ------------------------------------------------------------------ */
 /* Data-block constraints on the device entry (HHMM_PAIR_INVALID_DATA)   */
 /* ------------------------------------------------------------------ */
-thread_local bool t_data_checked_inline = false;
-
 constexpr int kDcSteps = 64; /* time steps per thread of data_check_kernel (per strip) */
 constexpr unsigned kDcMaxStrips = 32768; /* grid.y cap: longer series loop over strips */
 constexpr int kDcSeries = 4; /* series per thread (one 16-byte load per step) */
@@ -526,9 +394,7 @@ static hhmm_status launch_data_check(const DevArgs &a, const hhmm_request *req, 
 {
     const hhmm_data &d = req->data;
     const int m = req->model;
-    const bool discrete = m == HHMM_MODEL_HMM_MULTINOM || m == HHMM_MODEL_HMM_MULTINOM_SEMISUP ||
-                          m == HHMM_MODEL_TAYAL || m == HHMM_MODEL_TAYAL_LITE;
-    const bool tayal = m == HHMM_MODEL_TAYAL || m == HHMM_MODEL_TAYAL_LITE;
+    const bool discrete = is_discrete(m), tayal = is_tayal(m);
     hipError_t e = hipSuccess; /* a.dc_flag cleared by launch_all before the model's kernels */
     auto check = [&](const int32_t *v, int vhi, const int32_t *w, int whi, const int32_t *T, int Tmax) {
         const int64_t thr = (d.n_series + kDcSeries - 1) / kDcSeries;
@@ -537,8 +403,8 @@ static hhmm_status launch_data_check(const DevArgs &a, const hhmm_request *req, 
         hipLaunchKernelGGL(data_check_kernel, grid, dim3(256), 0, st, v, vhi, w, whi, T, (int64_t)d.n_series, Tmax,
                            a.dc_flag);
     };
-    /* the summary call's sweeps are not the ones that check x inline */
-    if (e == hipSuccess && discrete && (!inline_checked || a.seg_phase == 1))
+    /* inline_checked: one of the plan's sweeps checked x as it read it (never a segment window's) */
+    if (e == hipSuccess && discrete && !inline_checked)
         check(d.x_int, d.L, tayal ? d.sign : (m == HHMM_MODEL_HMM_MULTINOM_SEMISUP ? d.g : nullptr),
               tayal ? 2 : d.G, d.T, d.T_max);
     if (e == hipSuccess && m == HHMM_MODEL_TAYAL_LITE)
@@ -588,16 +454,13 @@ static hhmm_status run_iohmm_hat(const DevArgs &a, hipStream_t st, hhmm_status (
     return s;
 }
 
-static hhmm_status launch_model(const hhmm_request *req, const DevArgs &a, const hhmm_result *res, hipStream_t st);
+static hhmm_status launch_model(const hhmm_request *req, const DevArgs &a, const HmmPlan &p, const hhmm_result *res,
+                                hipStream_t st);
 
 hhmm_status launch_all(const hhmm_request *req, const hhmm_result *res, int64_t P, void *ws, hipStream_t st,
                        const hhmm_segment *seg, int seg_phase, bool check_data)
 {
     DevArgs a = make_args(req, res, P);
-    bind_workspace(a, ws, req->data.T_max, req->data.T_oos_max, (uint32_t)req->flags);
-    const bool check = check_data && a.dc_flag && (a.pair_status || (seg && seg_phase == 1 && seg->summary));
-    if (!check)
-        a.dc_flag = nullptr;
     if (seg) {
         a.seg_phase = seg_phase;
         a.seg_nofirst = !seg->first;
@@ -605,12 +468,15 @@ hhmm_status launch_all(const hhmm_request *req, const hhmm_result *res, int64_t 
         a.seg_sum = seg->summary;
         a.seg_enter = seg->enter;
         a.seg_leave = seg->leave;
-        if (a.scan_cl <= 0) {
-            set_error("segment: the request has no T-scan plan (HMM family, K <= 8, probability-space outputs)");
-            return HHMM_ERR_UNSUPPORTED;
-        }
     }
-    t_data_checked_inline = false;
+    const HmmPlan plan = bind_workspace(a, ws, req->data.T_max, req->data.T_oos_max, (uint32_t)req->flags);
+    const bool check = check_data && a.dc_flag && (a.pair_status || (seg && seg_phase == 1 && seg->summary));
+    if (!check)
+        a.dc_flag = nullptr;
+    if (seg && a.scan_cl <= 0) {
+        set_error("segment: the request has no T-scan plan (HMM family, K <= 8, probability-space outputs)");
+        return HHMM_ERR_UNSUPPORTED;
+    }
     if (check) { /* series flags: the inline checks of the model's sweeps, then data_check_kernel */
         const hipError_t e = hipMemsetAsync(a.dc_flag, 0, (size_t)req->data.n_series * sizeof(int32_t), st);
         if (e != hipSuccess) {
@@ -618,13 +484,14 @@ hhmm_status launch_all(const hhmm_request *req, const hhmm_result *res, int64_t 
             return HHMM_ERR_HIP;
         }
     }
-    hhmm_status s = launch_model(req, a, res, st);
+    hhmm_status s = launch_model(req, a, plan, res, st);
     if (s != HHMM_OK || !check)
         return s;
-    return launch_data_check(a, req, st, t_data_checked_inline);
+    return launch_data_check(a, req, st, plan.checked_inline);
 }
 
-static hhmm_status launch_model(const hhmm_request *req, const DevArgs &a, const hhmm_result *res, hipStream_t st)
+static hhmm_status launch_model(const hhmm_request *req, const DevArgs &a, const HmmPlan &p, const hhmm_result *res,
+                                hipStream_t st)
 {
     const bool lo = a.K <= 4;
     if (a.K > kMaxK) {
@@ -632,7 +499,7 @@ static hhmm_status launch_model(const hhmm_request *req, const DevArgs &a, const
             set_error("K = %d: the device path supports K <= %d", a.K, kMaxKLarge);
             return HHMM_ERR_UNSUPPORTED;
         }
-        if (is_iohmm_model(req->model))
+        if (is_iohmm(req->model))
             return run_iohmm_hat(a, st, run_large_iohmm);
         if (req->model != HHMM_MODEL_HMM_GAUSS && req->model != HHMM_MODEL_HMM_MULTINOM) {
             set_error("K = %d: the device path of model %d supports K <= %d", a.K, req->model, kMaxK);
@@ -641,12 +508,11 @@ static hhmm_status launch_model(const hhmm_request *req, const DevArgs &a, const
         return run_large(a, st);
     }
     switch (req->model) {
-    case HHMM_MODEL_HMM_GAUSS: return lo ? run_gauss_lo(a, req, res, st) : run_gauss_hi(a, req, res, st);
-    case HHMM_MODEL_HMM_MULTINOM: return lo ? run_multinom_lo(a, req, res, st) : run_multinom_hi(a, req, res, st);
-    case HHMM_MODEL_HMM_MULTINOM_SEMISUP:
-        return lo ? run_semisup_lo(a, req, res, st) : run_semisup_hi(a, req, res, st);
-    case HHMM_MODEL_TAYAL: return run_tayal(a, req, res, st);
-    case HHMM_MODEL_TAYAL_LITE: return run_tayal_lite(a, req, res, st);
+    case HHMM_MODEL_HMM_GAUSS: return (lo ? run_gauss_lo : run_gauss_hi)(a, p, req, res, st);
+    case HHMM_MODEL_HMM_MULTINOM: return (lo ? run_multinom_lo : run_multinom_hi)(a, p, req, res, st);
+    case HHMM_MODEL_HMM_MULTINOM_SEMISUP: return (lo ? run_semisup_lo : run_semisup_hi)(a, p, req, res, st);
+    case HHMM_MODEL_TAYAL: return run_tayal(a, p, req, res, st);
+    case HHMM_MODEL_TAYAL_LITE: return run_tayal_lite(a, p, req, res, st);
     case HHMM_MODEL_IOHMM_REG:
     case HHMM_MODEL_IOHMM_MIX:
     case HHMM_MODEL_IOHMM_HMIX:
@@ -656,6 +522,15 @@ static hhmm_status launch_model(const hhmm_request *req, const DevArgs &a, const
         set_error("model %d has no device path in this build", req->model);
         return HHMM_ERR_UNSUPPORTED;
     }
+}
+
+hhmm_status selftest_plan(const hhmm_request *req, int64_t P, char *buf, size_t n)
+{
+    static const hhmm_result none{};
+    DevArgs a = make_args(req, &none, P);
+    const HmmPlan p = bind_workspace(a, (void *)256, req->data.T_max, req->data.T_oos_max, (uint32_t)req->flags);
+    plan_line(p, bound_regions(a), buf, n);
+    return HHMM_OK;
 }
 
 hhmm_status selftest_cr_math(const double *in, double *out, int64_t n, int which)

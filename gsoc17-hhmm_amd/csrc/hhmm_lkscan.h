@@ -986,8 +986,8 @@ static hhmm_status run_large_model(const DevArgs &a, hipStream_t st)
 {
     constexpr bool discrete = !LkTraits<MODEL>::kGauss;
     const uint32_t out = a.outputs;
-    const uint32_t fb = HHMM_OUT_LOGLIK | HHMM_OUT_ALPHA | HHMM_OUT_BETA | HHMM_OUT_UNGAMMA | HHMM_OUT_GAMMA;
-    const uint32_t vit = HHMM_OUT_ZSTAR | HHMM_OUT_LOGP_ZSTAR;
+    const uint32_t fb = kOutFb & ~kOutLog;
+    const uint32_t vit = kOutVit;
     const uint32_t ffbs = HHMM_OUT_FFBS;
     if (a.scan_cl > 0 && discrete && a.L * 16 * ((KM + 15) / 16) * 4 * sizeof(double) > 64 * 1024) {
         set_error("K = %d: the parallel scan over T runs hmm-multinom with L <= %d", a.K, 64 * 1024 / (4 * 8 * 16 * ((KM + 15) / 16)));
@@ -995,7 +995,7 @@ static hhmm_status run_large_model(const DevArgs &a, hipStream_t st)
     }
     constexpr bool GS = LkTraits<MODEL>::kGauss;
     const size_t plds = discrete ? (size_t)4 * a.L * 16 * ((KM + 15) / 16) * sizeof(double) : 0;
-    const uint32_t logs = HHMM_OUT_UNALPHA | HHMM_OUT_UNBETA;
+    const uint32_t logs = kOutLog;
     if (out & ~(fb | vit | ffbs | logs)) {
         set_error("K = %d > %d: the large-K path evaluates loglik, unalpha, alpha, unbeta, beta, ungamma, gamma, "
                   "zstar, logp_zstar and z_ffbs", a.K, kMaxK);

@@ -3,9 +3,10 @@
 
 namespace hhmm {
 
-hhmm_status run_tayal(const DevArgs &a, const hhmm_request *req, const hhmm_result *res, hipStream_t st)
+hhmm_status run_tayal(const DevArgs &a, const HmmPlan &plan, const hhmm_request *req, const hhmm_result *res,
+                            hipStream_t st)
 {
-    return run_model_range<HHMM_MODEL_TAYAL, 4, 4>(a, req, res, st);
+    return run_model_range<HHMM_MODEL_TAYAL, 4, 4>(a, plan, req, res, st);
 }
 
 } // namespace hhmm

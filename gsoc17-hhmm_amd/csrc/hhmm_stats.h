@@ -138,18 +138,9 @@ inline DevArgs stats_dev_args(const hhmm_request *r, int64_t P, void *ws)
     return a;
 }
 
-/* Waves per workgroup, at most kBlock / 64, whose tables of per_wave bytes
- * each fit in LDS together (0: not even one), and the workgroup's LDS. */
-inline int waves_that_fit(size_t per_wave, size_t *lds)
-{
-    int waves = kBlock / 64;
-    while (waves > 0 && per_wave * waves > kLdsLimit)
-        --waves;
-    *lds = per_wave * waves;
-    return waves;
-}
-
-/* f(std::integral_constant<int, K>{}) for K in 1..kMaxK; false: K outside. */
+/* waves_that_fit and launch_status: hhmm_internal.h (the HMM family's launchers use them too).
+ *
+ * f(std::integral_constant<int, K>{}) for K in 1..kMaxK; false: K outside. */
 template <class F>
 bool dispatch_k(int K, F &&f)
 {
@@ -164,17 +155,6 @@ bool dispatch_k(int K, F &&f)
     case 8: f(std::integral_constant<int, 8>{}); return true;
     default: return false;
     }
-}
-
-/* After a launch: the launch error of `kernel`, if any. */
-inline hhmm_status launch_status(const char *kernel)
-{
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_error("%s launch: %s", kernel, hipGetErrorString(e));
-        return HHMM_ERR_HIP;
-    }
-    return HHMM_OK;
 }
 
 } // namespace hhmm

@@ -1397,10 +1397,8 @@ static hhmm_status launch_vscan(const DevArgs &a, hipStream_t st)
 {
     constexpr int KP = (K + 1) / 2;
     const size_t slab = ModelTraits<MODEL>::kDiscrete ? (size_t)a.L * KP * 64 * sizeof(double2) : 0;
-    if (slab * (kBlock / 64) > kLdsLimit) {
-        set_error("emission table K*L = %d*%d does not fit in LDS", a.K, a.L);
-        return HHMM_ERR_UNSUPPORTED;
-    }
+    if (slab * (kBlock / 64) > kLdsLimit)
+        return lds_fit_error(a.K, a.L);
     const int64_t lanes = a.P * a.vs_nc;
     const dim3 gc((unsigned)((lanes + kBlock - 1) / kBlock)), bc(kBlock);
     const dim3 gp((unsigned)((a.P + 63) / 64)), b64(64);

@@ -342,6 +342,9 @@ def declare(lib):
     lib.hhmm_selftest_shards.restype = C.c_int
     lib.hhmm_selftest_pipeline.argtypes = [RP, SP, C.c_int, C.c_int]
     lib.hhmm_selftest_pipeline.restype = C.c_int
+    if hasattr(lib, "hhmm_selftest_plan"):  # absent from libraries built before the launch plan (A/B variants)
+        lib.hhmm_selftest_plan.argtypes = [RP, C.c_char_p, C.c_size_t]
+        lib.hhmm_selftest_plan.restype = C.c_int
     QP = C.POINTER(SummaryRequest)
     lib.hhmm_summary.argtypes = [QP, C.c_void_p, C.c_void_p, C.c_int]
     lib.hhmm_summary.restype = C.c_int

@@ -399,6 +399,15 @@ hhmm_status hhmm_selftest_shards(const hhmm_request *req, hhmm_result *res, int 
  * every element exactly once. */
 hhmm_status hhmm_selftest_pipeline(const hhmm_request *req, hhmm_result *res, int nshards, int nchunks);
 
+/* Host-only self-test of the launch plan (no GPU used, nothing validated but
+ * NULL): what workspace sizing and dispatch decide for an HMM-family request at
+ * K <= 8, as one NUL-terminated line of key=value words in buf[n]: schedule,
+ * fb (kind), fb_mode (FbMode bits by name), oos_fb, vit (the Viterbi kind),
+ * scan_cl, scan_nc, vs_nc, regions (the workspace regions the planned kernels
+ * use), bound (the regions the workspace binding gives a pointer),
+ * checked_inline, side_stream.  Any other request: schedule=none. */
+hhmm_status hhmm_selftest_plan(const hhmm_request *req, char *buf, size_t n);
+
 #ifdef __cplusplus
 }
 #endif

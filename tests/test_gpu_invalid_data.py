@@ -52,10 +52,15 @@ def _corrupt(data, key, n, t, v):
 C2_PARS = ["loglik", "gamma_tk", "zstar_t", "logp_zstar"]
 
 
-@pytest.mark.parametrize("flags", [0, _abi.FLAG_VFB_OFF], ids=["phased-sweep", "two-kernels"])
+@pytest.mark.parametrize("flags", [0, _abi.FLAG_VFB_OFF, _abi.FLAG_FUSED | _abi.FLAG_VIT_LANES,
+                                   _abi.FLAG_FB_SPLIT | _abi.FLAG_VIT_LANES],
+                         ids=["phased-sweep", "two-kernels", "fused", "split"])
 def test_multinom_symbol_out_of_range(engine, oracle, flags):
     """C2's profile: the phased sweep checks x while it packs the symbols; with it off,
-    the separate check pass does."""
+    the separate check pass does.  The fused sweep (the plan's checked_inline = 0: the
+    check pass runs) and the split schedule (1: its forward launch checks x) at the same
+    shape; VIT_LANES keeps this batch of under 131072 pairs off the state-parallel
+    decoder, which would take it off both."""
     data, draws = synth.hmm_multinom(N=512, S=512, T=200, K=4, L=9)
     bad = _corrupt(data, "x", 37, 101, 10)       # L + 1
     bad = _corrupt(bad, "x", 200, 0, 0)          # below 1
