@@ -1769,6 +1769,7 @@ struct StatsEntry {
     /* the arrays of a host call: req / res on the host, dr / dq their device-side copies */
     void (*arrays)(const StatsEntry &en, const hhmm_request *req, const void *res, hhmm_request *dr, StatsResult *dq,
                    std::vector<StatsArr> &arrs);
+    int k_lo = 1, k_hi = kMaxK; /* the K its kernel takes (stats_check_k) */
 };
 
 template <class R, hhmm_status (*F)(const hhmm_request *, const R *)>
@@ -1905,6 +1906,18 @@ static const StatsEntry kEstep = {"E-step",
                                   typed_launch<hhmm_estep_result, launch_estep>,
                                   estep_workspace,
                                   estep_arrays};
+static size_t estep_large_workspace(const hhmm_request *req, int64_t P)
+{
+    return estep_large_workspace_bytes(req->data.K, req->data.T_max, P);
+}
+static const StatsEntry kEstepLarge = {"large-K E-step",
+                                       false,
+                                       typed_check<hhmm_estep_result, check_estep_large>,
+                                       typed_launch<hhmm_estep_result, launch_estep_large>,
+                                       estep_large_workspace,
+                                       estep_arrays,
+                                       kMaxK + 1,
+                                       kMaxKLarge};
 static const StatsEntry kDrawStats = {"draw statistics",
                                       true,
                                       typed_check<hhmm_estep_result, check_draw_stats>,
@@ -1964,10 +1977,8 @@ static hhmm_status stats_workspace_size(const StatsEntry &en, const hhmm_request
         set_error("request describes no pairs");
         return HHMM_ERR_INVALID_ARGUMENT;
     }
-    if (req->data.K > kMaxK) {
-        set_error("%s: K = %d, the lane-per-pair kernel supports K <= %d", en.name, req->data.K, kMaxK);
+    if (stats_check_k(en.name, req->data.K, en.k_lo, en.k_hi) != HHMM_OK)
         return HHMM_ERR_UNSUPPORTED;
-    }
     *bytes = en.workspace(req, P);
     return HHMM_OK;
 }
@@ -2064,6 +2075,20 @@ hhmm_status hhmm_estep_device(const hhmm_request *req, hhmm_estep_result *res, v
     return stats_device(kEstep, req, res, workspace, workspace_bytes_, stream);
 }
 hhmm_status hhmm_estep(const hhmm_request *req, hhmm_estep_result *res) { return stats_host(kEstep, req, res); }
+
+hhmm_status hhmm_estep_large_workspace_size(const hhmm_request *req, size_t *bytes)
+{
+    return stats_workspace_size(kEstepLarge, req, bytes);
+}
+hhmm_status hhmm_estep_large_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                                    size_t workspace_bytes_, void *stream)
+{
+    return stats_device(kEstepLarge, req, res, workspace, workspace_bytes_, stream);
+}
+hhmm_status hhmm_estep_large(const hhmm_request *req, hhmm_estep_result *res)
+{
+    return stats_host(kEstepLarge, req, res);
+}
 
 hhmm_status hhmm_draw_stats_workspace_size(const hhmm_request *req, size_t *bytes)
 {

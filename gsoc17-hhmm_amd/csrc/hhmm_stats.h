@@ -2,11 +2,12 @@
  * hhmm_stats.h -- host-side pieces shared by the "statistics per (series,
  * draw) pair" entries: the E-step (hhmm_estep.hip), the draw statistics
  * (hhmm_draw_stats.hip, hhmm_draw_stats_gauss.hip), the expected draw
- * statistics (hhmm_expect.hip), the IOHMM E-step (hhmm_estep_io.hip) and the
- * pointwise predictive densities (hhmm_pointwise.hip).  The
+ * statistics (hhmm_expect.hip), the IOHMM E-step (hhmm_estep_io.hip), the
+ * pointwise predictive densities (hhmm_pointwise.hip) and the E-step at
+ * 8 < K <= 32 (hhmm_estep_large.hip).  The
  * kernels differ; the argument checks, the DevArgs of a launch, the LDS fit,
  * the dispatch on K and the launch epilogue do not.  stats_check_tail belongs
- * to the four entries that fill an hhmm_estep_result; the IOHMM E-step and the
+ * to the five entries that fill an hhmm_estep_result; the IOHMM E-step and the
  * pointwise densities have a result struct and a tail of their own.  Not part of the public ABI.
  */
 #pragma once
@@ -22,7 +23,7 @@
 
 namespace hhmm {
 
-/* Each of the six entries gives the host path of hhmm_api.cpp (StatsEntry,
+/* Each of the seven entries gives the host path of hhmm_api.cpp (StatsEntry,
  * stats_*) a check_* and a launch_*; what those share follows them.
  *
  * Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
@@ -30,6 +31,13 @@ namespace hhmm {
 hhmm_status check_estep(const hhmm_request *r, const hhmm_estep_result *o);
 size_t estep_workspace_bytes(int K, int Tmax, int64_t P);
 hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws, hipStream_t st);
+
+/* Batched E-step at kMaxK < K <= kMaxKLarge (hhmm_estep_large.hip): the same
+ * three; the workspace is the forward checkpoints every kLChunk steps. */
+hhmm_status check_estep_large(const hhmm_request *r, const hhmm_estep_result *o);
+size_t estep_large_workspace_bytes(int K, int Tmax, int64_t P);
+hhmm_status launch_estep_large(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
+                               hipStream_t st);
 
 /* Draw statistics (hhmm_draw_stats.hip): argument checks (no device needed)
  * and the launch on `st` (device pointers); the workspace is the E-step's. */
@@ -67,8 +75,27 @@ hhmm_status launch_pointwise(const hhmm_request *r, const hhmm_pointwise_result 
 
 /* Head of an entry's check_*, in this order: NULL request, ABI, model id, the
  * entry's scope (`scope` says which models it takes and where the others go),
- * K, HHMM_DEVICE_SET.  `entry`: the entry's name in messages. */
-inline hhmm_status stats_check_head(const char *entry, const hhmm_request *r, bool (*model_ok)(int), const char *scope)
+ * K, HHMM_DEVICE_SET.  `entry`: the entry's name in messages.  k_lo..k_hi: the
+ * K the entry's kernel takes (the lane-per-pair kernels' 1..kMaxK unless given). */
+inline hhmm_status stats_check_k(const char *entry, int K, int k_lo, int k_hi)
+{
+    if (K > k_hi) {
+        if (k_hi == kMaxK)
+            set_error("%s: K = %d, the lane-per-pair kernel supports K <= %d", entry, K, kMaxK);
+        else
+            set_error("%s: K = %d, the state-parallel kernel supports %d <= K <= %d", entry, K, k_lo, k_hi);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    if (k_lo > 1 && K < k_lo) {
+        set_error("%s: K = %d, the state-parallel kernel supports %d <= K <= %d (hhmm_estep takes K <= %d)", entry, K,
+                  k_lo, k_hi, k_lo - 1);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    return HHMM_OK;
+}
+
+inline hhmm_status stats_check_head(const char *entry, const hhmm_request *r, bool (*model_ok)(int), const char *scope,
+                                    int k_lo = 1, int k_hi = kMaxK)
 {
     if (!r) {
         set_error("%s: request must be non-NULL", entry);
@@ -86,10 +113,8 @@ inline hhmm_status stats_check_head(const char *entry, const hhmm_request *r, bo
         set_error("%s: model %d is not supported (%s)", entry, r->model, scope);
         return HHMM_ERR_UNSUPPORTED;
     }
-    if (r->data.K > kMaxK) {
-        set_error("%s: K = %d, the lane-per-pair kernel supports K <= %d", entry, r->data.K, kMaxK);
+    if (stats_check_k(entry, r->data.K, k_lo, k_hi) != HHMM_OK)
         return HHMM_ERR_UNSUPPORTED;
-    }
     if (r->device == HHMM_DEVICE_SET) {
         set_error("%s: HHMM_DEVICE_SET is not supported (one device per call)", entry);
         return HHMM_ERR_UNSUPPORTED;

@@ -359,6 +359,12 @@ def declare(lib):
     lib.hhmm_estep_device.restype = C.c_int
     lib.hhmm_estep.argtypes = [RP, EP]
     lib.hhmm_estep.restype = C.c_int
+    lib.hhmm_estep_large_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
+    lib.hhmm_estep_large_workspace_size.restype = C.c_int
+    lib.hhmm_estep_large_device.argtypes = [RP, EP, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.hhmm_estep_large_device.restype = C.c_int
+    lib.hhmm_estep_large.argtypes = [RP, EP]
+    lib.hhmm_estep_large.restype = C.c_int
     # include/hhmm_gibbs.h (the result struct is the E-step's)
     lib.hhmm_draw_stats_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
     lib.hhmm_draw_stats_workspace_size.restype = C.c_int

@@ -22,6 +22,7 @@ def baum_welch(model, data, init, n_iter, pairing="zip", device=-1, lib=None):
     series).  Returns (params, trace): the parameters after the last M-step
     and the (n_iter, P) log-likelihoods of the parameters each iteration
     started from -- under exact arithmetic a non-decreasing sequence per pair.
+    hmm and hmm-multinom at K <= 32 (hhmm_estep_large above 8).
     A pair whose log-likelihood is not finite keeps NaN parameters from then
     on."""
     if model not in FIT_MODELS:

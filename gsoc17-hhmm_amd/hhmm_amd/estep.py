@@ -13,7 +13,8 @@ reference's drivers lack are plain arithmetic on these [P, K..] arrays:
 The statistics follow the CODED likelihood of each Stan program: hmm.stan:30
 adds sum_k normal_lpdf(x_1 | mu_k, sigma_k) to every state at t = 1 (quirk Q2),
 so x_1 enters w_k / s1_k / s2_k with weight 1 for every state.  hmm and
-hmm-multinom at K <= 8.
+hmm-multinom at K <= 32: hhmm_estep up to K = 8 (a lane per pair),
+hhmm_estep_large above (a group of 16 or 32 lanes per pair).
 
 score() and m_step() also take the statistics hhmm_amd.expected_stats returns
 for the two masked programs (FIT_MODELS): hmm-multinom-semisup with the
@@ -28,6 +29,13 @@ from .api import load_library
 MODELS = ("hmm", "hmm-multinom")
 FIT_MODELS = MODELS + ("hmm-multinom-semisup", "hhmm-tayal2009")  # score / m_step / baum_welch
 _TINY = 1e-300
+MAX_K_LANE = 8  # hhmm_estep: the lane-per-pair kernel (csrc kMaxK)
+
+
+def entry_name(K):
+    """The library entry estep() calls at K states: "estep" up to MAX_K_LANE,
+    "estep_large" above (K > 32 reaches the library, which rejects it)."""
+    return "estep" if int(K) <= MAX_K_LANE else "estep_large"
 
 
 def stat_shapes(model, P, K, L):
@@ -59,9 +67,11 @@ def estep(model, data, draws, pairing="grid", device=-1, lib=None, return_status
 
     Returns {name: array}: loglik (P,), n_1k (P, K), xi_ij (P, K, K) and c_kl
     (P, K, L) for hmm-multinom or w_k, s1_k, s2_k (P, K) for hmm.  A pair whose
-    log-likelihood is -inf or NaN has NaN statistics."""
+    log-likelihood is -inf or NaN has NaN statistics.  K <= 32; hhmm_estep_large
+    above 8."""
     lib = lib or load_library()
-    return _stats.call(lib, "estep", *prepare(model, data, draws, pairing, device), return_status)
+    pr, res, out = prepare(model, data, draws, pairing, device)
+    return _stats.call(lib, entry_name(pr.K), pr, res, out, return_status)
 
 
 def pair_draw(pairing, P, S, N):
@@ -84,8 +94,8 @@ def score(model, draws, stats, pairing, S, N):
     """Gradient of loglik with respect to the constrained parameters, per pair.
 
     {name: (P, ...)} for p_1k, A_ij and phi_k (hmm-multinom, semisup) or mu_k,
-    sigma_k (hmm), by Fisher's identity from the statistics of estep() or
-    expected_stats().  hhmm-tayal2009: p_11 (P,), n1[0] / p_11 - n1[2] / (1 -
+    sigma_k (hmm), by Fisher's identity from the statistics of estep() (K <= 32;
+    hhmm_estep_large above 8) or expected_stats().  hhmm-tayal2009: p_11 (P,), n1[0] / p_11 - n1[2] / (1 -
     p_11); A_row (P, 2, 2), (xi[0,1], xi[0,2]) / A_row[0] and (xi[2,0], xi[2,3])
     / A_row[1]; phi_k.  The simplex parameters are treated as free coordinates:
     a directional derivative along a tangent of the simplex is the matching
@@ -126,7 +136,8 @@ def _rows(counts, prev):
 
 
 def m_step(model, stats, prev=None):
-    """One Baum-Welch update from the statistics of estep(): per-pair parameters.
+    """One Baum-Welch update from the statistics of estep() (K <= 32;
+    hhmm_estep_large above 8): per-pair parameters.
 
     p_1k = n_1k; rows of A and phi are counts over their row sums (a row whose
     sum is 0 keeps its value in `prev`, {name: (P, ...)}); mu = s1 / w;

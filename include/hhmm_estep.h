@@ -33,6 +33,7 @@
  * 80 (two tables of one wave do not fit a CU's LDS) answer HHMM_ERR_UNSUPPORTED.
  * The request is the hhmm_request of hhmm.h; outputs, ffbs_u, hat_rand and the
  * scan flags are ignored (the E-step is sequential in T per pair).
+ * hmm and hmm-multinom at 8 < K <= 32 go to the hhmm_estep_large entries below.
  */
 #ifndef HHMM_ESTEP_H
 #define HHMM_ESTEP_H
@@ -72,6 +73,43 @@ hhmm_status hhmm_estep_device(const hhmm_request *req, hhmm_estep_result *res, v
  * rejects the request), uploads, runs on req->device (-1 = current), downloads
  * and synchronises. */
 hhmm_status hhmm_estep(const hhmm_request *req, hhmm_estep_result *res);
+
+/* The E-step at 8 < K <= 32 on the state-parallel groups (a group of 16 or 32
+ * lanes owns a pair, lane j state j): three entries with the signatures of the
+ * three above, filling the same hhmm_estep_result.
+ *
+ *   Models    hmm and hmm-multinom only.
+ *   K         9..32.  K <= 8 answers HHMM_ERR_UNSUPPORTED and names hhmm_estep;
+ *             K > 32 answers HHMM_ERR_UNSUPPORTED; both messages contain
+ *             "K = <value>".
+ *   Outputs   exactly those of hhmm_estep, with the same definitions: loglik,
+ *             n_1k = gamma_1, xi_ij = sum_{t>=2} P(z_{t-1} = i, z_t = j | x),
+ *             c_kl (hmm-multinom) or w_k, s1_k, s2_k (hmm; x_1 counts with
+ *             weight 1 for every state, Q2: w_k = 1 + sum_{t>=2} gamma_t(k)),
+ *             all pair-fastest [P, ...].  A zero in A_ij gives an exact zero in
+ *             xi_ij.
+ *   Request   every pairing, ragged T; sequential in T per pair: outputs,
+ *             ffbs_u, hat_rand and the scan flags are ignored.
+ *   NaN       a pair with a non-finite loglik, or with a step whose normaliser
+ *             is 0 or non-finite, gets NaN statistics; pair_status stays
+ *             HHMM_PAIR_OK.
+ *   Data      (device entry) a series whose symbols leave 1..L or whose T[n]
+ *             leaves 1..T_max sets pair_status = HHMM_PAIR_INVALID_DATA for its
+ *             pairs; the check runs on the observations as they are read, and
+ *             every emission lookup clamps its symbol.  The host entry rejects
+ *             such a request like hhmm_estep.
+ *   Device    HHMM_DEVICE_SET is unsupported, as for the other statistics
+ *             entries.
+ *   LDS       hmm-multinom keeps two [L][G] tables per group; an L whose tables
+ *             of one group exceed 160 KiB answers HHMM_ERR_UNSUPPORTED naming L.
+ *   Workspace the forward checkpoints, one K-vector per pair every 8 steps in
+ *             the [rows][K][P] layout: ceil(T_max / 8) * K * P * 8 bytes.
+ *   Bits      no floating-point atomics: both entries and every run give the
+ *             same bits. */
+hhmm_status hhmm_estep_large_workspace_size(const hhmm_request *req, size_t *bytes);
+hhmm_status hhmm_estep_large_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                                    size_t workspace_bytes, void *stream);
+hhmm_status hhmm_estep_large(const hhmm_request *req, hhmm_estep_result *res);
 
 #ifdef __cplusplus
 }

@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Times the batched E-step (hhmm_estep_device) beside the path a caller would
-otherwise take to the same statistics: hhmm_run_device with loglik | gamma_tk
-(whose [P, T, K] output then still has to be reduced).  Both at the C2 shape
-(hmm-multinom, K = 4, L = 9, 1M pairs x T = 1000, ZIP pairing), on the same
-device in the same run, device-resident inputs, events on torch's stream.
-Prints one JSON line.
+"""Times the batched E-step (hhmm_estep_device; hhmm_estep_large_device at
+K > 8) beside the path a caller would otherwise take to the same statistics:
+hhmm_run_device with loglik | gamma_tk (whose [P, T, K] output then still has
+to be reduced, and which leaves xi to the host).  Both at the C2 shape
+(hmm-multinom, K = 4, L = 9, 1M pairs x T = 1000, ZIP pairing) unless told
+otherwise, on the same device in the same run, device-resident inputs, events
+on torch's stream.  Prints one JSON line (--out: writes it to a file too).
 
     python tools/estep_bench.py
     python tools/estep_bench.py --pairs 65536 --T 256      # a smaller shape
+    python tools/estep_bench.py --K 23 --pairs 100000 --out profiles/estep_large_bench.json   # N1's scale
 
 Each measurement runs in a fresh child process under its own time limit
 (--step-timeout); after a child that fails or runs out of time nothing more is
@@ -85,11 +87,13 @@ def run_step(step, a):
         for k, v in bufs.items():
             setattr(res, k, v.data_ptr())
         res.pair_status = status.data_ptr()
-        assert lib.hhmm_estep_workspace_size(C.byref(req), C.byref(ws)) == 0, lib.hhmm_last_error().decode()
+        entry = "hhmm_" + sys.modules["hhmm_amd.estep"].entry_name(K)
+        assert getattr(lib, entry + "_workspace_size")(C.byref(req), C.byref(ws)) == 0, lib.hhmm_last_error().decode()
         wbuf = torch.empty(max(ws.value, 256), dtype=torch.uint8, device=dev)
+        run_device = getattr(lib, entry + "_device")
 
         def launch():
-            rc = lib.hhmm_estep_device(C.byref(req), C.byref(res), wbuf.data_ptr(), wbuf.numel(), st)
+            rc = run_device(C.byref(req), C.byref(res), wbuf.data_ptr(), wbuf.numel(), st)
             assert rc == 0, lib.hhmm_last_error().decode()
         written = 8.0 * sum(out.values())
     else:
@@ -124,6 +128,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--iters", type=int, default=7)
     ap.add_argument("--step-timeout", type=float, default=240.0, help="seconds per measurement (child process)")
+    ap.add_argument("--out", help="also write the JSON line to this file")
     ap.add_argument("--step", choices=STEPS, help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.step:
@@ -150,6 +155,8 @@ def main():
         out["same_loglik"] = abs(out["estep"]["loglik_mean"] - out["gamma"]["loglik_mean"]) <= 1e-9 * abs(
             out["gamma"]["loglik_mean"])
     print(json.dumps(out))
+    if a.out:
+        pathlib.Path(a.out).write_text(json.dumps(out, indent=1) + "\n")
     return rc
 
 
