@@ -1,13 +1,17 @@
 /*
- * hhmm_estep.hip -- gfx950 kernel of the batched E-step (include/hhmm_estep.h):
- * per (series, draw) pair the expected sufficient statistics summed over the
- * steps -- gamma_1, the pairwise posterior sum xi_ij and the emission sums --
- * for hmm and hmm-multinom at K <= 8.  Nothing is written per step.
+ * hhmm_estep.hip -- gfx950 kernel of the batched E-step (include/hhmm_estep.h)
+ * and of the expected draw statistics (include/hhmm_expect.h): per (series,
+ * draw) pair the expected sufficient statistics summed over the steps --
+ * gamma_1, the pairwise posterior sum xi_ij and the emission sums -- for hmm and
+ * hmm-multinom, and under the coded path weight (hhmm_gibbs.h's counts) for
+ * semisup and Tayal, at K <= 8.  Nothing is written per step.
  *
- * One LANE owns one pair (the layout and latency rules of hhmm_step.h, the
- * chunk helpers of hhmm_fbchunk.h).
- *   forward   fb_kernel's scaled linear-space sweep (fwd_chunk): a checkpoint
- *             of alpha every C = fb_chunk(K) steps, loglik at the end.
+ * One kernel template: the masked programs are `if constexpr` arms on kAux
+ * (kTayal where only Tayal differs).  One LANE owns one pair (the layout and
+ * latency rules of hhmm_step.h, the chunk helpers of hhmm_fbchunk.h).
+ *   forward   fb_kernel's scaled linear-space sweep (fwd_chunk applies the
+ *             masks; g / sign is loaded beside x): a checkpoint of alpha every
+ *             C = fb_chunk(K) steps, loglik at the end.
  *   backward  chunk by chunk from the end: alpha over the chunk is recomputed
  *             from its checkpoint, beta is carried.  The transition into step
  *             t >= 2 takes alpha_{t-1}, so a chunk handles the transitions
@@ -24,27 +28,41 @@
  *             gamma_1 = alpha_1 .* beta_1 / their sum.  A step with Z == 0 or
  *             a non-finite Z, or a non-finite loglik, makes the pair's
  *             statistics NaN.
+ * The masked programs take the ADJOINT of the masked forward step
+ * (expect_transition; bwd_step, the programs' own backward pass, is not:
+ * semisup's is unmasked, Tayal's masks on the previous state).
  * Accumulators: xi in K^2 fp64 registers (in LDS for the Gaussian kernels at
- * K >= 7, estep_xi_lds); the Gaussian sums in 3K registers;
- * c_kl in a second LDS slab per wave with the phi table's layout
- * (slab[(l * KP + kp) * 64 + lane], double2), so the update of row x_t is the
- * emission fetch's conflict-free 16-byte pattern.  Two slabs cost
- * 2 L ceil(K/2) KiB per wave; the workgroup is sized to fit 160 KiB.
+ * K >= 7, estep_xi_lds); the Gaussian sums in 3K registers; c_kl in a second
+ * LDS slab per wave with the phi table's layout (slab[(l * KP + kp) * 64 +
+ * lane], double2), so the update of row x_t is the emission fetch's
+ * conflict-free 16-byte pattern.  Two slabs cost 2 L ceil(K/2) KiB per wave;
+ * the workgroup is sized to fit 160 KiB.
  * The [P, ...] stores are pair-fastest: one coalesced wave transaction each.
  */
 #include <hip/hip_runtime.h>
 #include <math.h>
 
 #include "hhmm_estep.h"
+#include "hhmm_expect.h"
 #include "hhmm_fbchunk.h"
 #include "hhmm_stats.h"
 
 namespace hhmm {
 
+/* One struct per kernel-argument layout; EstepOutOf picks by the model. */
 struct EstepOut {
     double *loglik, *n1, *xi, *c, *w, *s1, *s2;
     int32_t *status;
 };
+
+struct ExpectOut {
+    double *loglik, *n1, *xi, *c;
+    int32_t *status;
+    int32_t ahi; /* the auxiliary stream's upper bound: G (semisup), 2 (Tayal) */
+};
+
+template <int MODEL>
+using EstepOutOf = std::conditional_t<ModelTraits<MODEL>::kAux, ExpectOut, EstepOut>;
 
 /* xi lives in LDS instead of registers (xs[(i * K + j) * 64 + lane]) where the
  * registers do not hold it: the Gaussian kernels at K >= 7, whose per-state
@@ -110,6 +128,151 @@ __device__ __forceinline__ double estep_transition(const PairParams<MODEL, K> &p
     return Z;
 }
 
+/* beta_{t-1}(i) under per-lane masks, in the split form -- b divided by the
+ * mask once per step, then K FMAs per row: 2K selects -- or with a select per
+ * term (K^2 selects, K^2 extra adds).  The K >= 6 instances are past 256 VGPRs
+ * and keep the select form: with the split form hipcc's allocation of them
+ * left a dword in a private segment, which no instance may have. */
+constexpr bool expect_split(int K) { return K <= 5; }
+
+/* The adjoint transition into a step with emission e and observation o:
+ * accumulates xi (without its constant factor A) and returns the step's gamma
+ * in g; be: beta_t in, beta_{t-1} out.  Returns Z.  SG: the step's Tayal sign
+ * class when the wave shares it (tayal_dispatch), else -1 (the masks per lane).
+ * With on(j) the forward mask of step t at state j and b = e_t .* beta_t:
+ *     beta_{t-1}(i) = sum_{j on} A(i,j) b(j) + sum_{j off} b(j)
+ *     Z             = sum_i alpha_{t-1}(i) beta_{t-1}(i),   a = alpha_{t-1} / Z
+ *     gamma_t(j)    = b(j) (on(j) ? sum_i a(i) A(i,j) : sum_i a(i))
+ *     xi(i,j)      += on(j) ? a(i) b(j) : 0
+ * Where every lane of the wave has the step's sign (one series under many
+ * draws) the masks are compile-time constants and the structural zeros of A
+ * are skipped -- only under skip_ok, see tayal_nz. */
+template <int MODEL, int K, int SG>
+__device__ __forceinline__ double expect_transition(const PairParams<MODEL, K> &pp, const double (&ap)[K],
+                                                    const double (&e)[K], const Obs &o, double (&be)[K],
+                                                    double (&xi)[K][K], double (&g)[K])
+{
+    constexpr bool KNOWN = SG > 0 && ModelTraits<MODEL>::kTayal;
+    double b[K], bn[K];
+    bool on[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        b[j] = e[j] * be[j];
+        if constexpr (KNOWN)
+            on[j] = tayal_on(SG, j);
+        else if constexpr (ModelTraits<MODEL>::kSemisup)
+            on[j] = semisup_mask(o.aux, j);
+        else
+            on[j] = tayal_pred(o.aux, j);
+    }
+    if constexpr (KNOWN) {
+        /* the split form with the masks known: the same additions in the same
+         * order (the per-lane form's other terms are exact zeros) -- the same
+         * bits, so a pair's result does not depend on its wave's other lanes */
+        static_assert(expect_split(K), "the sign-class arms mirror the split form");
+        double boff = 0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+            if (!on[j])
+                boff += b[j];
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            double acc = boff;
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+                if (on[j] && tayal_nz(i, j < 4 ? j : 0))
+                    acc = fma(pp.A[i][j], b[j], acc);
+            bn[i] = acc;
+        }
+    } else if constexpr (expect_split(K)) {
+        /* b split by the mask: the "on" part takes A, the "off" part is one scalar */
+        double bon[K], boff = 0.0;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            bon[j] = on[j] ? b[j] : 0.0;
+            boff += on[j] ? 0.0 : b[j];
+        }
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            double acc = fma(pp.A[i][0], bon[0], boff);
+#pragma unroll
+            for (int j = 1; j < K; ++j)
+                acc = fma(pp.A[i][j], bon[j], acc);
+            bn[i] = acc;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            double acc = 0.0;
+            bool first = true;
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const double t = first ? pp.A[i][j] * b[j] : fma(pp.A[i][j], b[j], acc);
+                const double u = first ? b[j] : acc + b[j];
+                acc = on[j] ? t : u;
+                first = false;
+            }
+            bn[i] = acc;
+        }
+    }
+    double Z = ap[0] * bn[0];
+#pragma unroll
+    for (int i = 1; i < K; ++i)
+        Z = fma(ap[i], bn[i], Z);
+    const double r = 1.0 / Z;
+    double apr[K];
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+        apr[i] = ap[i] * r;
+    double tot = apr[0];
+#pragma unroll
+    for (int i = 1; i < K; ++i)
+        tot += apr[i];
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        double sj = 0.0;
+        bool first = true;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            if (KNOWN && (!on[j] || !tayal_nz(i < 4 ? i : 0, j < 4 ? j : 0)))
+                continue;
+            sj = first ? apr[i] * pp.A[i][j] : fma(apr[i], pp.A[i][j], sj);
+            first = false;
+        }
+        g[j] = (on[j] ? sj : tot) * b[j];
+    }
+    /* A is constant over the steps: xi accumulates alpha_{t-1}(i) b_t(j) / Z over
+     * the "on" steps and takes its factor A(i,j) once, at the end */
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if (KNOWN && !on[j])
+            continue;
+        const double bm = on[j] ? b[j] : 0.0;
+#pragma unroll
+        for (int i = 0; i < K; ++i) {
+            if (KNOWN && !tayal_nz(i < 4 ? i : 0, j < 4 ? j : 0))
+                continue;
+            xi[i][j] = fma(apr[i], bm, xi[i][j]);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < K; ++i)
+        be[i] = bn[i];
+    int ex = 0;
+    renorm<K>(be, ex);
+    return Z;
+}
+
+/* xcheck_acc for the auxiliary stream: the running max of aux - 1 (unsigned,
+ * so a value below 1 wraps above every bound) over the lane's own steps */
+template <int C, bool FULL>
+__device__ __forceinline__ void auxcheck_acc(uint32_t &am, const Obs (&o)[C], int c, int Tp)
+{
+#pragma unroll
+    for (int v = 0; v < C; ++v)
+        am = max(am, (FULL || c * C + v < Tp) ? ((uint32_t)o[v].aux - 1u) : 0u);
+}
+
 /* gamma of one step into the emission sums: row x of the c_kl slab (clamped
  * like the emission fetch), or the Gaussian moments. */
 template <int MODEL, int K>
@@ -140,11 +303,12 @@ __device__ __forceinline__ void estep_emit_acc(double2 *cslab, int L, const Obs 
 }
 
 template <int MODEL, int K>
-__global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const EstepOut o)
+__global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const EstepOutOf<MODEL> o)
 {
     constexpr int C = fb_chunk(K);
     constexpr int KP = (K + 1) / 2;
     constexpr bool GAUSS = ModelTraits<MODEL>::kGauss;
+    constexpr bool AUX = ModelTraits<MODEL>::kAux;
     HIP_DYNAMIC_SHARED(double2, lds)
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -171,7 +335,10 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
     ln.slab = pslab;
     load_params<MODEL, K, false>(ln.pp, a, d);
     if constexpr (!GAUSS) {
-        fill_table<K, false>(pslab, a, d);
+        if constexpr (AUX)
+            ln.pp.skip_ok &= fill_table<K, false>(pslab, a, d);
+        else
+            fill_table<K, false>(pslab, a, d);
         for (int i = 0; i < a.L * KP; ++i)
             cslab[i * 64] = make_double2(0.0, 0.0);
     }
@@ -182,15 +349,15 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
         for (int i = 0; i < K * K; ++i)
             xs[i * 64] = 0.0;
     }
-    const SeriesPtrs sp = series_ptrs<MODEL, false>(a, n);
+    const SeriesPtrs sp = series_ptrs<MODEL, AUX>(a, n);
     const int Tw_min = wave_min(ln.Tp);
     const int Tw_max = wave_max(ln.Tp);
     const int nfull = Tw_min / C;            /* chunks complete for every lane */
     const int nchunk = (Tw_max + C - 1) / C; /* chunks any lane needs: <= ceil(Tmax / C) checkpoint rows */
 
-    /* ---- forward sweep: fb_kernel's, checkpoints only ---- */
+    /* ---- forward sweep: fb_kernel's (masked), checkpoints only ---- */
     double ll;
-    uint32_t xm = 0;
+    uint32_t xm = 0, am = 0;
     Obs cur[C];
     {
         double al[K];
@@ -203,7 +370,7 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
         Obs grp[D][C];
 #pragma unroll
         for (int i = 0; i < D; ++i)
-            load_chunk<MODEL, C, false>(grp[i], sp, i * C);
+            load_chunk<MODEL, C, AUX>(grp[i], sp, i * C);
         Em<K> ecur;
         emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, grp[0][0], ecur);
         int c = 0;
@@ -211,7 +378,7 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
             Obs nxt[D][C];
 #pragma unroll
             for (int i = 0; i < D; ++i)
-                load_chunk<MODEL, C, false>(nxt[i], sp, (c + D + i) * C);
+                load_chunk<MODEL, C, AUX>(nxt[i], sp, (c + D + i) * C);
 #pragma unroll
             for (int i = 0; i < D; ++i) {
                 fwd_chunk<MODEL, K, C, FB_GAMMA, true>(a, ln, c + i, grp[i],
@@ -219,6 +386,8 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
                                                        al, lsc, ex);
                 if constexpr (!GAUSS)
                     xcheck_acc<C, true>(xm, grp[i], c + i, ln.Tp);
+                if constexpr (AUX)
+                    auxcheck_acc<C, true>(am, grp[i], c + i, ln.Tp);
             }
 #pragma unroll
             for (int i = 0; i < D; ++i)
@@ -231,10 +400,12 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
             cur[u] = grp[0][u];
         for (; c < nchunk; ++c) {
             Obs nxt[C];
-            load_chunk<MODEL, C, false>(nxt, sp, (c + 1) * C);
+            load_chunk<MODEL, C, AUX>(nxt, sp, (c + 1) * C);
             fwd_chunk<MODEL, K, C, FB_GAMMA, false>(a, ln, c, cur, nxt[0], ecur, al, lsc, ex);
             if constexpr (!GAUSS)
                 xcheck_acc<C, false>(xm, cur, c, ln.Tp);
+            if constexpr (AUX)
+                auxcheck_acc<C, false>(am, cur, c, ln.Tp);
 #pragma unroll
             for (int u = 0; u < C; ++u)
                 cur[u] = nxt[u];
@@ -253,9 +424,10 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
             xi[i][j] = 0.0;
     }
     bool bad = !__builtin_isfinite(ll);
-    double x0 = 0.0;
+    double x0 = 0.0; /* x_1 (Gaussian) */
+    int aux1 = 0;    /* g_1 / sign_1 */
     const int clast = nchunk - 1;
-    load_chunk<MODEL, C, false>(cur, sp, clast * C);
+    load_chunk<MODEL, C, AUX>(cur, sp, clast * C);
     /* checkpoint rows are wave-uniform: a lane shorter than the wave reads
      * (unused) slots past its own last chunk, never past the allocation */
     double ck[K];
@@ -266,7 +438,7 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
     for (int c = clast; c >= 0; --c) {
         const int t0 = c * C;
         Obs nxt[C];
-        load_chunk<MODEL, C, false>(nxt, sp, (c - 1) * C);
+        load_chunk<MODEL, C, AUX>(nxt, sp, (c - 1) * C);
         double cn[K];
 #pragma unroll
         for (int k = 0; k < K; ++k)
@@ -284,8 +456,16 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
             for (int u = 1; u < C; ++u) {
                 Em<K> enx;
                 emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, cur[u + 1 < C ? u + 1 : u], enx);
-                if (t0 + u < ln.Tp)
-                    fwd_step_to<MODEL, K>(abuf[u - 1], abuf[u], ln.pp, ecur.e, cur[u], exb);
+                if (t0 + u < ln.Tp) {
+                    /* Tayal: fwd_step_to without its sign-class dispatch (the same
+                     * bits): the recompute of a chunk stays straight-line code */
+                    if constexpr (ModelTraits<MODEL>::kTayal) {
+                        fwd_step_raw<MODEL, K>(abuf[u - 1], abuf[u], ln.pp, ecur.e, cur[u]);
+                        renorm<K>(abuf[u], exb);
+                    } else {
+                        fwd_step_to<MODEL, K>(abuf[u - 1], abuf[u], ln.pp, ecur.e, cur[u], exb);
+                    }
+                }
                 ecur = enx;
             }
         }
@@ -299,7 +479,14 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
             emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, cur[v - 1 >= 1 ? v - 1 : 1], enx);
             if (t0 + v < ln.Tp) {
                 double g[K];
-                const double Z = estep_transition<MODEL, K>(ln.pp, abuf[v - 1], ecur.e, be, xi, xs, g);
+                double Z = 0.0;
+                if constexpr (AUX)
+                    tayal_dispatch<MODEL>(ob, ln.pp.skip_ok, [&](auto sgc) {
+                        Z = expect_transition<MODEL, K, decltype(sgc)::value>(ln.pp, abuf[v - 1], ecur.e, ob, be, xi,
+                                                                              g);
+                    });
+                else
+                    Z = estep_transition<MODEL, K>(ln.pp, abuf[v - 1], ecur.e, be, xi, xs, g);
                 bad |= !((Z > 0.0) & (Z < __builtin_inf()));
                 estep_emit_acc<MODEL, K>(cslab, a.L, ob, g, w, s1, s2);
             }
@@ -321,6 +508,8 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
                 x0 = cur[0].xr;
             else
                 estep_emit_acc<MODEL, K>(cslab, a.L, cur[0], n1, w, s1, s2);
+            if constexpr (AUX)
+                aux1 = cur[0].aux;
         }
         onext = cur[0];
 #pragma unroll
@@ -336,14 +525,23 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
     const double nanv = dev_nan();
     put_out(o.loglik, po, ll);
 #pragma unroll
-    for (int k = 0; k < K; ++k)
-        put_out(o.n1 + a.P * (int64_t)k, po, bad ? nanv : n1[k]);
+    for (int k = 0; k < K; ++k) {
+        bool p1 = true; /* Tayal: the init factor p_1k applies at (sign_1, k) */
+        if constexpr (ModelTraits<MODEL>::kTayal)
+            p1 = tayal_init_pred(aux1, k);
+        put_out(o.n1 + a.P * (int64_t)k, po, bad ? nanv : p1 ? n1[k] : 0.0);
+    }
 #pragma unroll
     for (int j = 0; j < K; ++j)
 #pragma unroll
-        for (int i = 0; i < K; ++i)
-            put_out(o.xi + a.P * (int64_t)(i + K * j), po,
-                    bad ? nanv : ln.pp.A[i][j] * (XL ? xs[(i * K + j) * 64] : xi[i][j]));
+        for (int i = 0; i < K; ++i) {
+            if constexpr (AUX) /* an entry no step switched on is 0 whatever A(i,j) is */
+                put_out(o.xi + a.P * (int64_t)(i + K * j), po,
+                        bad ? nanv : xi[i][j] != 0.0 ? ln.pp.A[i][j] * xi[i][j] : 0.0);
+            else
+                put_out(o.xi + a.P * (int64_t)(i + K * j), po,
+                        bad ? nanv : ln.pp.A[i][j] * (XL ? xs[(i * K + j) * 64] : xi[i][j]));
+        }
     if constexpr (GAUSS) {
 #pragma unroll
         for (int k = 0; k < K; ++k) {
@@ -364,13 +562,15 @@ __global__ void __launch_bounds__(kBlock) estep_kernel(const DevArgs a, const Es
     }
     if (o.status) {
         bool inv = !GAUSS && xm >= (uint32_t)a.L;
+        if constexpr (AUX) /* the whole expression: `inv |= am >= ahi` on the line above moves nine listings */
+            inv = xm >= (uint32_t)a.L || am >= (uint32_t)o.ahi;
         if (a.T)
             inv |= a.T[n] < 1 || a.T[n] > a.Tmax;
         o.status[p] = inv ? HHMM_PAIR_INVALID_DATA : HHMM_PAIR_OK;
     }
 }
 
-/* Waves per workgroup and its LDS: two slabs per wave for hmm-multinom. */
+/* Waves per workgroup and its LDS: two slabs per wave for the discrete programs. */
 static int estep_waves(int model, int K, int L, size_t *lds)
 {
     if (model == HHMM_MODEL_HMM_GAUSS) { /* K >= 7: xi in LDS (estep_xi_lds) */
@@ -387,59 +587,104 @@ size_t estep_workspace_bytes(int K, int Tmax, int64_t P)
     return (size_t)estep_chunks(K, Tmax) * (size_t)K * (size_t)P * sizeof(double);
 }
 
+/* Both check_*: the entry's scope, then the LDS fit of the discrete programs' two tables of one wave. */
+static hhmm_status estep_check(const char *entry, const hhmm_request *r, const hhmm_estep_result *o,
+                               bool (*model_ok)(int), const char *scope)
+{
+    const hhmm_status s = stats_check_head(entry, r, model_ok, scope);
+    if (s != HHMM_OK)
+        return s;
+    size_t lds;
+    if (r->model != HHMM_MODEL_HMM_GAUSS && r->data.K >= 1 && r->data.L >= 1 &&
+        estep_waves(r->model, r->data.K, r->data.L, &lds) < 1) {
+        set_error("%s: L * ceil(K / 2) = %d * %d > 80: the emission table and its count table of one wave "
+                  "do not fit in LDS",
+                  entry, r->data.L, (r->data.K + 1) / 2);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    return stats_check_tail(entry, r, o, false);
+}
+
 static bool estep_model(int m) { return m == HHMM_MODEL_HMM_GAUSS || m == HHMM_MODEL_HMM_MULTINOM; }
 
 hhmm_status check_estep(const hhmm_request *r, const hhmm_estep_result *o)
 {
-    const hhmm_status s = stats_check_head("E-step", r, estep_model,
-                                           "hmm and hmm-multinom only; the semisup and Tayal backward passes are "
-                                           "not the adjoint of their forward");
-    if (s != HHMM_OK)
-        return s;
-    if (r->model == HHMM_MODEL_HMM_MULTINOM && r->data.K >= 1 && r->data.L >= 1) {
-        size_t lds;
-        if (estep_waves(r->model, r->data.K, r->data.L, &lds) < 1) {
-            set_error("E-step: L * ceil(K / 2) = %d * %d > 80: the emission table and its count table of one wave "
-                      "do not fit in LDS",
-                      r->data.L, (r->data.K + 1) / 2);
-            return HHMM_ERR_UNSUPPORTED;
-        }
-    }
-    return stats_check_tail("E-step", r, o, false);
+    return estep_check("E-step", r, o, estep_model, "hmm and hmm-multinom only; the semisup and Tayal backward "
+                                                    "passes are not the adjoint of their forward");
+}
+
+static bool expect_model(int m)
+{
+    return m == HHMM_MODEL_HMM_MULTINOM || m == HHMM_MODEL_HMM_MULTINOM_SEMISUP || m == HHMM_MODEL_TAYAL;
+}
+
+hhmm_status check_expected_stats(const hhmm_request *r, const hhmm_estep_result *o)
+{
+    return estep_check("expected statistics", r, o, expect_model,
+                       "hmm-multinom, hmm-multinom-semisup and hhmm-tayal2009 only; the Gaussian hmm has hhmm_estep");
 }
 
 template <int MODEL>
-static bool launch_estep_m(const DevArgs &a, const EstepOut &o, dim3 grid, dim3 block, size_t lds, hipStream_t st)
+static bool launch_estep_m(const DevArgs &a, const EstepOutOf<MODEL> &o, dim3 grid, dim3 block, size_t lds,
+                           hipStream_t st)
 {
     return dispatch_k(a.K, [&](auto kc) {
         hipLaunchKernelGGL((estep_kernel<MODEL, decltype(kc)::value>), grid, block, lds, st, a, o);
     });
 }
 
-hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws, hipStream_t st)
+/* The one launch path of both entries (`entry`: the entry's name in messages). */
+static hhmm_status launch_estep_any(const char *entry, const hhmm_request *r, const hhmm_estep_result *res, int64_t P,
+                                    void *ws, hipStream_t st)
 {
     DevArgs a = stats_dev_args(r, P, ws);
-    a.x = r->data.x_int;
+    a.x = r->data.x_int; /* hmm and hmm-multinom */
     a.xr = r->data.x_real;
     a.phi_k = r->draws.phi_k;
     a.mu_k = r->draws.mu_k;
     a.sigma_k = r->draws.sigma_k;
-    EstepOut o{res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->w_k, res->s1_k, res->s2_k, res->pair_status};
+    a.g = r->data.g; /* semisup (g) and Tayal (sign, p_11, A_row) */
+    a.sign = r->data.sign;
+    a.p_11 = r->draws.p_11;
+    a.A_row = r->draws.A_row;
+    const EstepOut eo{res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->w_k, res->s1_k, res->s2_k, res->pair_status};
+    const ExpectOut xo{res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->pair_status,
+                       r->model == HHMM_MODEL_TAYAL ? 2 : r->data.G};
     size_t lds = 0;
     const int waves = estep_waves(a.model, a.K, a.L, &lds);
     if (waves < 1) {
-        set_error("E-step: the tables of K*L = %d*%d do not fit in LDS", a.K, a.L);
+        set_error("%s: the tables of K*L = %d*%d do not fit in LDS", entry, a.K, a.L);
         return HHMM_ERR_UNSUPPORTED;
     }
     const int threads = 64 * waves;
     const dim3 grid((unsigned)((P + threads - 1) / threads)), block(threads);
-    const bool ok = a.model == HHMM_MODEL_HMM_GAUSS ? launch_estep_m<HHMM_MODEL_HMM_GAUSS>(a, o, grid, block, lds, st)
-                                                    : launch_estep_m<HHMM_MODEL_HMM_MULTINOM>(a, o, grid, block, lds, st);
+    bool ok = false;
+    if (a.model == HHMM_MODEL_HMM_GAUSS)
+        ok = launch_estep_m<HHMM_MODEL_HMM_GAUSS>(a, eo, grid, block, lds, st);
+    else if (a.model == HHMM_MODEL_HMM_MULTINOM)
+        ok = launch_estep_m<HHMM_MODEL_HMM_MULTINOM>(a, eo, grid, block, lds, st);
+    else if (a.model == HHMM_MODEL_HMM_MULTINOM_SEMISUP)
+        ok = launch_estep_m<HHMM_MODEL_HMM_MULTINOM_SEMISUP>(a, xo, grid, block, lds, st);
+    else if (a.model == HHMM_MODEL_TAYAL && a.K == 4) {
+        hipLaunchKernelGGL((estep_kernel<HHMM_MODEL_TAYAL, 4>), grid, block, lds, st, a, xo);
+        ok = true;
+    }
     if (!ok) {
-        set_error("E-step: K = %d outside 1..%d", a.K, kMaxK);
+        set_error("%s: model %d at K = %d has no kernel (K outside 1..%d)", entry, a.model, a.K, kMaxK);
         return HHMM_ERR_UNSUPPORTED;
     }
     return launch_status("estep_kernel");
+}
+
+hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws, hipStream_t st)
+{
+    return launch_estep_any("E-step", r, res, P, ws, st);
+}
+
+hhmm_status launch_expected_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
+                                  hipStream_t st)
+{
+    return launch_estep_any("expected statistics", r, res, P, ws, st);
 }
 
 } // namespace hhmm

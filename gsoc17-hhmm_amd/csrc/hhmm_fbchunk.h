@@ -5,9 +5,9 @@
  * (emit_alpha, emit_posteriors), FbLane, and one checkpoint chunk of the
  * forward sweep (fwd_chunk) and of the backward sweep (bwd_chunk, with
  * ffbs_draw), and the LDS copy of the exp2 table the Gaussian FFBS filter
- * reads (fb_exp2_lds, kExp2TabBytes).  fb_kernel (hhmm_fb.h) and the four statistics kernels
- * (hhmm_estep.hip, hhmm_expect.hip, hhmm_draw_stats.hip,
- * hhmm_draw_stats_gauss.hip) run their own sweeps over these chunks; the
+ * reads (fb_exp2_lds, kExp2TabBytes).  fb_kernel (hhmm_fb.h) and the two statistics kernel
+ * templates (estep_kernel in hhmm_estep.hip, draw_stats_kernel in
+ * hhmm_draw_stats.hip) run their own sweeps over these chunks; the
  * statistics kernels include this header and nothing beyond it.
  */
 #pragma once

@@ -1,8 +1,8 @@
 /*
  * hhmm_stats.h -- host-side pieces shared by the "statistics per (series,
- * draw) pair" entries: the E-step (hhmm_estep.hip), the draw statistics
- * (hhmm_draw_stats.hip, hhmm_draw_stats_gauss.hip), the expected draw
- * statistics (hhmm_expect.hip), the IOHMM E-step (hhmm_estep_io.hip), the
+ * draw) pair" entries: the E-step and the expected draw statistics
+ * (hhmm_estep.hip), the draw statistics of the discrete programs and of the
+ * Gaussian hmm (hhmm_draw_stats.hip), the IOHMM E-step (hhmm_estep_io.hip), the
  * pointwise predictive densities (hhmm_pointwise.hip) and the E-step at
  * 8 < K <= 32 (hhmm_estep_large.hip).  The
  * kernels differ; the argument checks, the DevArgs of a launch, the LDS fit,
@@ -45,15 +45,15 @@ hhmm_status check_draw_stats(const hhmm_request *r, const hhmm_estep_result *o);
 hhmm_status launch_draw_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                               hipStream_t st);
 
-/* Gaussian draw statistics (hhmm_draw_stats_gauss.hip): the same pair for
- * hmm.stan; the workspace is the E-step's. */
+/* Gaussian draw statistics (hhmm_draw_stats.hip, the same kernel template):
+ * the same pair for hmm.stan; the workspace is the E-step's. */
 hhmm_status check_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_result *o);
 hhmm_status launch_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                                     hipStream_t st);
 
-/* Expected draw statistics (hhmm_expect.hip): argument checks (no device
- * needed) and the launch on `st` (device pointers); the workspace is the
- * E-step's, and hmm-multinom goes to launch_estep. */
+/* Expected draw statistics (hhmm_estep.hip, the E-step's kernel template and
+ * launch path): argument checks (no device needed) and the launch on `st`
+ * (device pointers); the workspace is the E-step's. */
 hhmm_status check_expected_stats(const hhmm_request *r, const hhmm_estep_result *o);
 hhmm_status launch_expected_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                                   hipStream_t st);

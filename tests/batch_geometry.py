@@ -1,10 +1,11 @@
 """Large batches of the five "statistics per (series, draw) pair" entries built from a few base pairs
 (test helper of tests/test_stats_geometry.py; a plain module).
 
-The entries' kernels (csrc/hhmm_estep.hip, hhmm_expect.hip, hhmm_draw_stats.hip, hhmm_draw_stats_gauss.hip,
-hhmm_estep_io.hip) give one lane to one pair, carve a per-wave LDS slab at `wave * elems` and address a
-pair by `gwave = blockIdx.x * nw + wave`.  A numpy reference of a 577-pair batch would be slow, so the
-batch is made of B <= 32 BASE pairs (a zip request with N = S = B, referenced once) and an index vector:
+The entries' kernels (csrc/hhmm_estep.hip for the E-step and the expected statistics, hhmm_draw_stats.hip for
+both draw statistics entries, hhmm_estep_io.hip) give one lane to one pair, carve a per-wave LDS slab at
+`wave * elems` and address a pair by `gwave = blockIdx.x * nw + wave`.  A numpy reference of a 577-pair
+batch would be slow, so the batch is made of B <= 32 BASE pairs (a zip request with N = S = B, referenced
+once) and an index vector:
 
     make_base(entry, shape)   the base pairs, their lengths and roles, the uniforms of the two draw entries
     reference(base, ...)      their reference statistics, from the existing reference modules
@@ -12,7 +13,7 @@ batch is made of B <= 32 BASE pairs (a zip request with N = S = B, referenced on
     layout(P, classes)        idx, wave by wave: wave j takes its 64 pairs from class j % 3
 
 Lengths.  C = fb_chunk(K) steps per forward chunk; the forward sweep takes the full chunks D at a time
-(kFwdGroup = 4 in csrc/hhmm_fbchunk.h; hhmm_draw_stats_gauss.hip takes D = 2 at K = 8) while
+(kFwdGroup = 4 in csrc/hhmm_fbchunk.h; the Gaussian draw statistics take D = 2 at K = 8) while
 c + D <= nfull = (shortest lane of the wave) / C, then a guarded tail up to ceil(longest lane / C).
     long    D C, D C + 1, (D + 1) C - 1, (D + 1) C + 1, 2 D C + C + 3 = T_max
     short   1, 2, C, C + 1
