@@ -1769,7 +1769,8 @@ struct StatsEntry {
     /* the arrays of a host call: req / res on the host, dr / dq their device-side copies */
     void (*arrays)(const StatsEntry &en, const hhmm_request *req, const void *res, hhmm_request *dr, StatsResult *dq,
                    std::vector<StatsArr> &arrs);
-    int k_lo = 1, k_hi = kMaxK; /* the K its kernel takes (stats_check_k) */
+    int k_lo = 1, k_hi = kMaxK;       /* the K its kernel takes (stats_check_k) */
+    const char *below = "hhmm_estep"; /* the entry that takes K < k_lo */
 };
 
 template <class R, hhmm_status (*F)(const hhmm_request *, const R *)>
@@ -1930,6 +1931,19 @@ static const StatsEntry kDrawStatsGauss = {"Gaussian draw statistics",
                                            typed_launch<hhmm_estep_result, launch_draw_stats_gauss>,
                                            estep_workspace,
                                            estep_arrays};
+static size_t draw_stats_large_workspace(const hhmm_request *req, int64_t P)
+{
+    return draw_stats_large_workspace_bytes(req->data.K, req->data.T_max, P);
+}
+static const StatsEntry kDrawStatsLarge = {"large-K draw statistics",
+                                           true,
+                                           typed_check<hhmm_estep_result, check_draw_stats_large>,
+                                           typed_launch<hhmm_estep_result, launch_draw_stats_large>,
+                                           draw_stats_large_workspace,
+                                           estep_arrays,
+                                           kMaxK + 1,
+                                           kMaxKLarge,
+                                           "hhmm_draw_stats / hhmm_draw_stats_gauss"};
 static const StatsEntry kExpectedStats = {"expected statistics",
                                           false,
                                           typed_check<hhmm_estep_result, check_expected_stats>,
@@ -1977,7 +1991,7 @@ static hhmm_status stats_workspace_size(const StatsEntry &en, const hhmm_request
         set_error("request describes no pairs");
         return HHMM_ERR_INVALID_ARGUMENT;
     }
-    if (stats_check_k(en.name, req->data.K, en.k_lo, en.k_hi) != HHMM_OK)
+    if (stats_check_k(en.name, req->data.K, en.k_lo, en.k_hi, en.below) != HHMM_OK)
         return HHMM_ERR_UNSUPPORTED;
     *bytes = en.workspace(req, P);
     return HHMM_OK;
@@ -2116,6 +2130,20 @@ hhmm_status hhmm_draw_stats_gauss_device(const hhmm_request *req, hhmm_estep_res
 hhmm_status hhmm_draw_stats_gauss(const hhmm_request *req, hhmm_estep_result *res)
 {
     return stats_host(kDrawStatsGauss, req, res);
+}
+
+hhmm_status hhmm_draw_stats_large_workspace_size(const hhmm_request *req, size_t *bytes)
+{
+    return stats_workspace_size(kDrawStatsLarge, req, bytes);
+}
+hhmm_status hhmm_draw_stats_large_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                                         size_t workspace_bytes_, void *stream)
+{
+    return stats_device(kDrawStatsLarge, req, res, workspace, workspace_bytes_, stream);
+}
+hhmm_status hhmm_draw_stats_large(const hhmm_request *req, hhmm_estep_result *res)
+{
+    return stats_host(kDrawStatsLarge, req, res);
 }
 
 hhmm_status hhmm_expected_stats_workspace_size(const hhmm_request *req, size_t *bytes)

@@ -3,11 +3,12 @@
  * draw) pair" entries: the E-step and the expected draw statistics
  * (hhmm_estep.hip), the draw statistics of the discrete programs and of the
  * Gaussian hmm (hhmm_draw_stats.hip), the IOHMM E-step (hhmm_estep_io.hip), the
- * pointwise predictive densities (hhmm_pointwise.hip) and the E-step at
- * 8 < K <= 32 (hhmm_estep_large.hip).  The
+ * pointwise predictive densities (hhmm_pointwise.hip), the E-step at
+ * 8 < K <= 32 (hhmm_estep_large.hip) and the draw statistics there
+ * (hhmm_draw_stats_large.hip).  The
  * kernels differ; the argument checks, the DevArgs of a launch, the LDS fit,
  * the dispatch on K and the launch epilogue do not.  stats_check_tail belongs
- * to the five entries that fill an hhmm_estep_result; the IOHMM E-step and the
+ * to the six entries that fill an hhmm_estep_result; the IOHMM E-step and the
  * pointwise densities have a result struct and a tail of their own.  Not part of the public ABI.
  */
 #pragma once
@@ -23,7 +24,7 @@
 
 namespace hhmm {
 
-/* Each of the seven entries gives the host path of hhmm_api.cpp (StatsEntry,
+/* Each of the eight entries gives the host path of hhmm_api.cpp (StatsEntry,
  * stats_*) a check_* and a launch_*; what those share follows them.
  *
  * Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
@@ -51,6 +52,14 @@ hhmm_status check_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_resul
 hhmm_status launch_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                                     hipStream_t st);
 
+/* Draw statistics at kMaxK < K <= kMaxKLarge (hhmm_draw_stats_large.hip), hmm
+ * and hmm-multinom: the same pair; the workspace is the forward checkpoints
+ * every kLChunk steps (the large-K E-step's size). */
+hhmm_status check_draw_stats_large(const hhmm_request *r, const hhmm_estep_result *o);
+size_t draw_stats_large_workspace_bytes(int K, int Tmax, int64_t P);
+hhmm_status launch_draw_stats_large(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
+                                    hipStream_t st);
+
 /* Expected draw statistics (hhmm_estep.hip, the E-step's kernel template and
  * launch path): argument checks (no device needed) and the launch on `st`
  * (device pointers); the workspace is the E-step's. */
@@ -76,8 +85,9 @@ hhmm_status launch_pointwise(const hhmm_request *r, const hhmm_pointwise_result 
 /* Head of an entry's check_*, in this order: NULL request, ABI, model id, the
  * entry's scope (`scope` says which models it takes and where the others go),
  * K, HHMM_DEVICE_SET.  `entry`: the entry's name in messages.  k_lo..k_hi: the
- * K the entry's kernel takes (the lane-per-pair kernels' 1..kMaxK unless given). */
-inline hhmm_status stats_check_k(const char *entry, int K, int k_lo, int k_hi)
+ * K the entry's kernel takes (the lane-per-pair kernels' 1..kMaxK unless given);
+ * `below`: the entry a message names for K < k_lo. */
+inline hhmm_status stats_check_k(const char *entry, int K, int k_lo, int k_hi, const char *below = "hhmm_estep")
 {
     if (K > k_hi) {
         if (k_hi == kMaxK)
@@ -87,15 +97,15 @@ inline hhmm_status stats_check_k(const char *entry, int K, int k_lo, int k_hi)
         return HHMM_ERR_UNSUPPORTED;
     }
     if (k_lo > 1 && K < k_lo) {
-        set_error("%s: K = %d, the state-parallel kernel supports %d <= K <= %d (hhmm_estep takes K <= %d)", entry, K,
-                  k_lo, k_hi, k_lo - 1);
+        set_error("%s: K = %d, the state-parallel kernel supports %d <= K <= %d (%s takes K <= %d)", entry, K, k_lo,
+                  k_hi, below, k_lo - 1);
         return HHMM_ERR_UNSUPPORTED;
     }
     return HHMM_OK;
 }
 
 inline hhmm_status stats_check_head(const char *entry, const hhmm_request *r, bool (*model_ok)(int), const char *scope,
-                                    int k_lo = 1, int k_hi = kMaxK)
+                                    int k_lo = 1, int k_hi = kMaxK, const char *below = "hhmm_estep")
 {
     if (!r) {
         set_error("%s: request must be non-NULL", entry);
@@ -113,7 +123,7 @@ inline hhmm_status stats_check_head(const char *entry, const hhmm_request *r, bo
         set_error("%s: model %d is not supported (%s)", entry, r->model, scope);
         return HHMM_ERR_UNSUPPORTED;
     }
-    if (stats_check_k(entry, r->data.K, k_lo, k_hi) != HHMM_OK)
+    if (stats_check_k(entry, r->data.K, k_lo, k_hi, below) != HHMM_OK)
         return HHMM_ERR_UNSUPPORTED;
     if (r->device == HHMM_DEVICE_SET) {
         set_error("%s: HHMM_DEVICE_SET is not supported (one device per call)", entry);

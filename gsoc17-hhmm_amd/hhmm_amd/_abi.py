@@ -372,6 +372,13 @@ def declare(lib):
     lib.hhmm_draw_stats_device.restype = C.c_int
     lib.hhmm_draw_stats.argtypes = [RP, EP]
     lib.hhmm_draw_stats.restype = C.c_int
+    # the same header: hmm-multinom and hmm at 8 < K <= 32
+    lib.hhmm_draw_stats_large_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
+    lib.hhmm_draw_stats_large_workspace_size.restype = C.c_int
+    lib.hhmm_draw_stats_large_device.argtypes = [RP, EP, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.hhmm_draw_stats_large_device.restype = C.c_int
+    lib.hhmm_draw_stats_large.argtypes = [RP, EP]
+    lib.hhmm_draw_stats_large.restype = C.c_int
     # include/hhmm_gibbs_gauss.h (the result struct is the E-step's)
     lib.hhmm_draw_stats_gauss_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
     lib.hhmm_draw_stats_gauss_workspace_size.restype = C.c_int

@@ -1,6 +1,6 @@
 """What the "statistics per (series, draw) pair" entries share on the Python side.
 
-hhmm_estep, hhmm_estep_large, hhmm_draw_stats, hhmm_draw_stats_gauss and hhmm_expected_stats take
+hhmm_estep, hhmm_estep_large, hhmm_draw_stats, hhmm_draw_stats_gauss, hhmm_draw_stats_large and hhmm_expected_stats take
 an hhmm_request and fill an hhmm_estep_result (include/hhmm_estep.h);
 hhmm_estep_io fills its own hhmm_estep_io_result (`result_cls`).  They differ in the draw arrays they read, the statistics they return and whether
 they consume uniforms.  `request()` builds the pair with the shape checks,

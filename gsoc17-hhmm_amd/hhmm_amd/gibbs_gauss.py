@@ -38,10 +38,19 @@ import numpy as np
 
 from . import _stats
 from .api import load_library
-from .gibbs import _dirichlet, _fortran_flat, stack_chains  # noqa: F401  (stack_chains: reused as is)
+from .gibbs import _check_support, _dirichlet, _fortran_flat, stack_chains  # noqa: F401  (stack_chains: reused as is)
 
 MODEL = "hmm"
 PARAMS = ("p_1k", "A_ij", "mu_k", "sigma_k")
+SUPPORTED = ("p_1k", "A_ij")  # the parameters `support` can restrict: the two simplexes
+MAX_K_LANE = 8  # hhmm_draw_stats_gauss: the lane-per-pair kernel (csrc kMaxK)
+
+
+def entry_name(K):
+    """The library entry draw_stats_gauss() and gibbs_gauss() call at K states:
+    "draw_stats_gauss" up to MAX_K_LANE, "draw_stats_large" above (K > 32
+    reaches the library, which rejects it)."""
+    return "draw_stats_gauss" if int(K) <= MAX_K_LANE else "draw_stats_large"
 
 
 def param_shapes(S, K):
@@ -74,9 +83,11 @@ def draw_stats_gauss(data, draws, uniforms, pairing="grid", device=-1, lib=None,
     shape (P, T_max), values in (0, 1].  Returns {name: array}: loglik (P,), n_1k
     (P, K), xi_ij (P, K, K), w_k, s1_k, s2_k (P, K) as float64; x_1 counts once
     for every state.  A pair whose log-likelihood is not finite, or whose draw is
-    undefined at some step, has NaN statistics."""
+    undefined at some step, has NaN statistics.  K <= 32; hhmm_draw_stats_large
+    above 8."""
     lib = lib or load_library()
-    return _stats.call(lib, "draw_stats_gauss", *prepare(data, draws, uniforms, pairing, device), return_status)
+    pr, res, out = prepare(data, draws, uniforms, pairing, device)
+    return _stats.call(lib, entry_name(pr.K), pr, res, out, return_status)
 
 
 def _nig_prior(prior):
@@ -104,7 +115,7 @@ def _prior_tensors(torch, prior, dtype, device):
                  for v in nig + (prior.get("p_1k", 1.0), prior.get("A_ij", 1.0)))
 
 
-def _conditional(torch, stats, pt, generator):
+def _conditional(torch, stats, pt, generator, support=None):
     m0, k0, a0, b0, cp, cA = pt
     n1, xi, w, s1, s2 = (stats[k] for k in ("n_1k", "xi_ij", "w_k", "s1_k", "s2_k"))
     kn = k0 + w
@@ -116,11 +127,13 @@ def _conditional(torch, stats, pt, generator):
     sig2 = torch.where(bad, torch.full_like(bn, float("nan")), bn / g)
     eps = torch.randn(sig2.shape, dtype=sig2.dtype, device=sig2.device, generator=generator)
     mu = mn + torch.sqrt(sig2 / kn) * eps
-    return {"p_1k": _dirichlet(torch, n1 + cp, generator), "A_ij": _dirichlet(torch, xi + cA, generator),
+    support = support or {}
+    return {"p_1k": _dirichlet(torch, n1 + cp, generator, support.get("p_1k"), n1),
+            "A_ij": _dirichlet(torch, xi + cA, generator, support.get("A_ij"), xi),
             "mu_k": mu, "sigma_k": torch.sqrt(sig2)}
 
 
-def conditional_draw_gauss(stats, prior, generator=None):
+def conditional_draw_gauss(stats, prior, generator=None, support=None):
     """theta | z for hmm.stan: one draw of the parameters of every pair from its statistics.
 
     stats: {n_1k (P, K), xi_ij (P, K, K), w_k, s1_k, s2_k (P, K)} as torch
@@ -132,11 +145,14 @@ def conditional_draw_gauss(stats, prior, generator=None):
     (P, ...) tensors: p_1k ~ Dir(a + n_1k), every row of A_ij ~ Dir(a + xi[i, :]),
     sigma_k^2 ~ InvGamma(an, bn), mu_k ~ N(mn, sigma_k^2 / kn) (the module
     docstring has an, bn, kn, mn).  A pair with NaN statistics gets NaN
-    parameters."""
+    parameters.  support: {"p_1k": mask, "A_ij": mask}, the structural zeros of
+    the two simplexes as gibbs.conditional_draw takes them (exact zeros outside,
+    rows drawn over their support, NaN for a count outside it); None is the
+    unrestricted draw, bit for bit."""
     import torch
     st = {k: torch.as_tensor(stats[k]) for k in ("n_1k", "xi_ij", "w_k", "s1_k", "s2_k")}
     pt = _prior_tensors(torch, prior, st["w_k"].dtype, st["w_k"].device)
-    return _conditional(torch, st, pt, generator)
+    return _conditional(torch, st, pt, generator, _check_support(support, SUPPORTED))
 
 
 def _label_symmetric(prior, P, K):
@@ -170,7 +186,8 @@ def relabel_ordered(draws):
     return out
 
 
-def gibbs_gauss(data, init, n_iter, burn=0, thin=1, prior=None, seed=0, pairing="zip", relabel=False, lib=None):
+def gibbs_gauss(data, init, n_iter, burn=0, thin=1, prior=None, seed=0, pairing="zip", relabel=False, lib=None,
+                support=None):
     """n_iter sweeps of the blocked Gibbs sampler of hmm.stan for every pair, on the device.
 
     The structure of gibbs(): every pair is a chain with its own parameters, so
@@ -178,8 +195,9 @@ def gibbs_gauss(data, init, n_iter, burn=0, thin=1, prior=None, seed=0, pairing=
     The data goes to the device once and the parameters stay there.  One sweep
     draws the uniforms u = 1 - torch.rand(P * T_max) (in (0, 1]), takes the
     statistics of the path they select (hhmm_draw_stats_gauss_device on torch's
-    current stream) and redraws the parameters (conditional_draw_gauss's
-    update).  prior["mu_sigma"] is required.  relabel=True sorts the kept draws
+    current stream; hhmm_draw_stats_large_device at 8 < K <= 32) and redraws the
+    parameters (conditional_draw_gauss's update; `support` is its argument).
+    prior["mu_sigma"] is required.  relabel=True sorts the kept draws
     by mu_k (relabel_ordered) and needs a label-symmetric prior: the same
     (m0, kappa0, a0, b0) for every state, a scalar p_1k concentration and a
     scalar or diagonal / off-diagonal A_ij concentration (ValueError otherwise).
@@ -199,13 +217,18 @@ def gibbs_gauss(data, init, n_iter, burn=0, thin=1, prior=None, seed=0, pairing=
     if relabel and not _label_symmetric(prior, P, K):
         raise ValueError("gibbs_gauss: relabel=True needs a prior that is the same for every state (sorting by mu_k "
                          "is exact only when the posterior is invariant under label permutations)")
+    if relabel and _check_support(support, SUPPORTED):
+        raise ValueError("gibbs_gauss: relabel=True cannot be combined with support (a mask ties the parameters to "
+                         "the labels, so the posterior is not invariant under label permutations)")
     import torch
     lib = lib or load_library()
     dev = torch.device("cuda", torch.cuda.current_device())
     # the request's arrays on the device (the parameters: updated in place every sweep)
     ubuf = torch.empty(P * Tmax, dtype=torch.float64, device=dev)
     pr.req.ffbs_u = ubuf.data_ptr()
-    run = _stats.DeviceStats(lib, "draw_stats_gauss", pr, res, stat_shapes(P, K))
+    run = _stats.DeviceStats(lib, entry_name(K), pr, res, stat_shapes(P, K))
+    support = {name: torch.as_tensor(np.asarray(m, dtype=bool), device=dev)
+               for name, m in _check_support(support, SUPPORTED).items()}
     pbuf, sbuf = run.arrays, run.out
     views = {"n_1k": sbuf["n_1k"].view(K, P).t(), "xi_ij": sbuf["xi_ij"].view(K, K, P).permute(2, 1, 0)}
     for name in ("w_k", "s1_k", "s2_k"):
@@ -220,7 +243,7 @@ def gibbs_gauss(data, init, n_iter, burn=0, thin=1, prior=None, seed=0, pairing=
         ubuf.neg_().add_(1.0)
         run.run()
         trace[it] = sbuf["loglik"]
-        new = _conditional(torch, views, pt, gen)
+        new = _conditional(torch, views, pt, gen, support)
         for name in PARAMS:
             pbuf[name].copy_(_fortran_flat(new[name]))
             if it >= burn and (it - burn) % thin == 0:

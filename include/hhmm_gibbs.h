@@ -41,6 +41,10 @@
  * count tables (32-bit) in LDS: the bound is
  *   L * (4 * ceil(K / 2) + K) + K * K <= 640      (units of 256 bytes, 160 KiB)
  * i.e. L <= 24 at K = 8, L <= 52 at K = 4.
+ *
+ * 8 < K <= 32: hhmm_draw_stats_large (below) takes hmm-multinom and the
+ * Gaussian hmm (hhmm_gibbs_gauss.h has its statistics) there, on groups of 16
+ * or 32 lanes per pair.
  */
 #ifndef HHMM_GIBBS_H
 #define HHMM_GIBBS_H
@@ -69,6 +73,34 @@ hhmm_status hhmm_draw_stats_device(const hhmm_request *req, hhmm_estep_result *r
  * rejects the request), uploads, runs on req->device (-1 = current), downloads
  * and synchronises. */
 hhmm_status hhmm_draw_stats(const hhmm_request *req, hhmm_estep_result *res);
+
+/*
+ * The same statistics at 9 <= K <= 32, for hmm-multinom (loglik, n_1k, xi_ij,
+ * c_kl as above) and for the Gaussian hmm (loglik, n_1k, xi_ij, w_k, s1_k, s2_k
+ * as hhmm_gibbs_gauss.h defines them; the arrays of the other family are
+ * ignored and may be NULL).  A group of G lanes owns a pair, lane j state j:
+ * G = 16 up to K = 16, G = 32 above.  z is the path hhmm_run returns as z_ffbs
+ * at these K for the same request and uniforms, bit for bit, and loglik comes
+ * from that same filter.  NaN statistics, ffbs_u, the pairings, ragged T and
+ * HHMM_PAIR_INVALID_DATA on the device entry are as above.
+ *
+ * Scope: hmm-multinom-semisup and hhmm-tayal2009 are K <= 8 programs and answer
+ * HHMM_ERR_UNSUPPORTED here, as do the IOHMMs, K <= 8 (hhmm_draw_stats and
+ * hhmm_draw_stats_gauss take those), K > 32 and HHMM_DEVICE_SET.  hmm-multinom:
+ * one group keeps two exchange slots and its emission table (fp64), the
+ * table's counts and its K rows of xi (32-bit) in LDS, and one group must fit a
+ * CU's 160 KiB:
+ *   G * (16 + 12 * L + 4 * K) <= 163840 bytes
+ * i.e. L <= 848 at K = 12 (G = 16) and L <= 417 at K = 25 (G = 32); a larger L
+ * answers HHMM_ERR_UNSUPPORTED, before the device is looked at.
+ *
+ * The workspace is the forward checkpoints, one every 8 steps:
+ *   ceil(T_max / 8) * K * P * 8 bytes.
+ */
+hhmm_status hhmm_draw_stats_large_workspace_size(const hhmm_request *req, size_t *bytes);
+hhmm_status hhmm_draw_stats_large_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                                         size_t workspace_bytes, void *stream);
+hhmm_status hhmm_draw_stats_large(const hhmm_request *req, hhmm_estep_result *res);
 
 #ifdef __cplusplus
 }

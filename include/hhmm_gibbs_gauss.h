@@ -45,6 +45,12 @@
  * Scope: HHMM_MODEL_HMM_GAUSS at 1 <= K <= 8, every pairing, ragged T, one
  * device.  Every other model, K > 8 and HHMM_DEVICE_SET answer
  * HHMM_ERR_UNSUPPORTED (the discrete programs: hhmm_gibbs.h).
+ *
+ * 8 < K <= 32: hhmm_draw_stats_large, hhmm_draw_stats_large_device and
+ * hhmm_draw_stats_large_workspace_size (declared in hhmm_gibbs.h, one entry
+ * for hmm-multinom and for this model) return the statistics above, with the
+ * same definitions, order of summation and NaN rule, from the state-parallel
+ * kernel.
  */
 #ifndef HHMM_GIBBS_GAUSS_H
 #define HHMM_GIBBS_GAUSS_H

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""Times the draw statistics (hhmm_draw_stats_device) beside the path a caller
-had before it: hhmm_run_device with loglik | z_ffbs, then a torch reduction of
-the [P, T] path to the same counts.  Also one full Gibbs sweep: the uniforms,
-the draw statistics and the conjugate updates.  All at the C2 shape
-(hmm-multinom, K = 4, L = 9, 1M pairs x T = 1000, ZIP pairing) on one device,
-device-resident inputs, events on torch's stream, the paths interleaved in one
-process: every round times each of them once.  Prints one JSON line.
+"""Times the draw statistics (hhmm_draw_stats_device; hhmm_draw_stats_large_device
+at K > 8) beside the path a caller had before it: hhmm_run_device with loglik |
+z_ffbs, then a torch reduction of the [P, T] path to the same counts.  Also one
+full Gibbs sweep: the uniforms, the draw statistics and the conjugate updates.
+All at the C2 shape (hmm-multinom, K = 4, L = 9, 1M pairs x T = 1000, ZIP
+pairing) on one device, device-resident inputs, events on torch's stream, the
+paths interleaved in one process: every round times each of them once.  Prints
+one JSON line.
 
     python tools/draw_stats_bench.py
     python tools/draw_stats_bench.py --pairs 65536 --T 256      # a smaller shape
+    python tools/draw_stats_bench.py --K 23 --pairs 100000      # the large-K shape of estep_bench.py --K 23
 
 The measurement runs in a child process under a time limit (--step-timeout).
 """
@@ -48,6 +50,7 @@ def run_child(a):
     lib = hhmm_amd.load_library()
     assert lib.hhmm_init(1) == 0, lib.hhmm_last_error().decode()
     P, T, K, L = a.pairs, a.T, a.K, a.L
+    entry = "hhmm_draw_stats" if K <= 8 else "hhmm_draw_stats_large"
     req, keep, dev = device_request(torch, P, T, K, L)
     st = torch.cuda.current_stream().cuda_stream
     gen = torch.Generator(device=dev)
@@ -69,11 +72,13 @@ def run_child(a):
     sstat = torch.zeros(P, dtype=torch.int32, device=dev)
     sres.pair_status = sstat.data_ptr()
     ws_a = C.c_size_t(0)
-    assert lib.hhmm_draw_stats_workspace_size(C.byref(req), C.byref(ws_a)) == 0, lib.hhmm_last_error().decode()
+    assert getattr(lib, entry + "_workspace_size")(C.byref(req), C.byref(ws_a)) == 0, lib.hhmm_last_error().decode()
     wa = torch.empty(max(ws_a.value, 256), dtype=torch.uint8, device=dev)
 
+    stats_device = getattr(lib, entry + "_device")
+
     def stats():
-        rc = lib.hhmm_draw_stats_device(C.byref(req), C.byref(sres), wa.data_ptr(), wa.numel(), st)
+        rc = stats_device(C.byref(req), C.byref(sres), wa.data_ptr(), wa.numel(), st)
         assert rc == 0, lib.hhmm_last_error().decode()
 
     # (b) the path itself, then its reduction in torch
@@ -155,14 +160,20 @@ def main():
     if a.child:
         run_child(a)
         return 0
-    K, L, C_ = a.K, a.L, (8 if a.K <= 4 else 4)
+    K, L, C_ = a.K, a.L, (8 if a.K <= 4 or a.K > 8 else 4)
     out = {"shape": {"model": "hmm-multinom", "pairing": "zip", "pairs": a.pairs, "T": a.T, "K": K, "L": L}}
     # bytes each path moves per (pair, step): x twice (forward, backward), u, the checkpoints out and back;
     # the parent's path also writes z, and its reduction reads z and x again (temporaries not counted)
     ck = 2 * 8.0 * K / C_
     out["bytes_per_step"] = {"stats": 4 + 4 + 8 + ck, "path": 4 + 4 + 8 + ck + 4, "reduce_at_least": 4 + 4}
-    per_wave = L * (1024 * ((K + 1) // 2) + 256 * K) + 256 * K * K
-    out["lds_bytes_per_wave"] = {"stats": per_wave, "path": L * 1024 * ((K + 1) // 2)}
+    if K <= 8:
+        per_wave = L * (1024 * ((K + 1) // 2) + 256 * K) + 256 * K * K
+        out["lds_bytes_per_wave"] = {"stats": per_wave, "path": L * 1024 * ((K + 1) // 2)}
+    else:  # a group of G lanes per pair: slots, phi table, its counts and the xi rows against slots and phi table
+        G = 16 if K <= 16 else 32
+        out["lds_bytes_per_group"] = {"stats": G * (16 + 12 * L + 4 * K), "path": G * (16 + 8 * L)}
+    # what each route writes: the statistics, or the path itself
+    out["bytes_written"] = {"stats": a.pairs * (1 + K + K * K + K * L) * 8, "path": 4 * a.pairs * a.T}
     cmd = [sys.executable, __file__, "--child"] + [f"--{k}={getattr(a, k)}" for k in
                                                    ("pairs", "T", "K", "L", "warmup", "iters")]
     try:
