@@ -1956,6 +1956,15 @@ static const StatsEntry kPointwise = {"pointwise",
                                       typed_launch<hhmm_pointwise_result, launch_pointwise>,
                                       pointwise_workspace_bytes,
                                       pointwise_arrays};
+static const StatsEntry kPointwiseLarge = {"large-K pointwise",
+                                           false,
+                                           typed_check<hhmm_pointwise_result, check_pointwise_large>,
+                                           typed_launch<hhmm_pointwise_result, launch_pointwise_large>,
+                                           pointwise_large_workspace_bytes,
+                                           pointwise_arrays,
+                                           kMaxK + 1,
+                                           kMaxKLarge,
+                                           "hhmm_pointwise"};
 static const StatsEntry kEstepIo = {"IOHMM E-step",
                                     false,
                                     typed_check<hhmm_estep_io_result, check_estep_io>,
@@ -2186,6 +2195,20 @@ hhmm_status hhmm_pointwise_device(const hhmm_request *req, hhmm_pointwise_result
 hhmm_status hhmm_pointwise(const hhmm_request *req, hhmm_pointwise_result *res)
 {
     return stats_host(kPointwise, req, res);
+}
+
+hhmm_status hhmm_pointwise_large_workspace_size(const hhmm_request *req, size_t *bytes)
+{
+    return stats_workspace_size(kPointwiseLarge, req, bytes);
+}
+hhmm_status hhmm_pointwise_large_device(const hhmm_request *req, hhmm_pointwise_result *res, void *workspace,
+                                        size_t workspace_bytes_, void *stream)
+{
+    return stats_device(kPointwiseLarge, req, res, workspace, workspace_bytes_, stream);
+}
+hhmm_status hhmm_pointwise_large(const hhmm_request *req, hhmm_pointwise_result *res)
+{
+    return stats_host(kPointwiseLarge, req, res);
 }
 
 } // extern "C"

@@ -284,29 +284,12 @@ static size_t dsl_group_lds(int model, int K, int L)
     return (2 + tabs) * G * sizeof(double) + (tabs + (size_t)K) * G * sizeof(uint32_t);
 }
 
-/* Threads per workgroup and its LDS (launch_estep_large's rule): kBlock halved
- * down to one group until the groups' LDS (hmm: beside the workgroup's det-exp
- * table) fits (0: one group does not); whole workgroups share a CU's LDS, so
- * among the sizes of at least one wave the one that lets the most waves (up to
- * two per SIMD) be resident is taken, the larger on a tie. */
+/* Threads per workgroup and its LDS: group_threads' rule (hhmm_stats.h), the
+ * groups' LDS beside the workgroup's det-exp table for hmm. */
 static int dsl_threads(int model, int K, int L, size_t *lds)
 {
-    const int G = dsl_G(K);
-    const size_t per = dsl_group_lds(model, K, L);
     const size_t tab = model == HHMM_MODEL_HMM_GAUSS ? kDslTabBytes : 0;
-    int threads = kBlock;
-    while (threads > G && tab + (size_t)(threads / G) * per > kLdsLimit)
-        threads /= 2;
-    size_t best = 0;
-    for (int t = threads; t >= 64; t /= 2) {
-        const size_t waves = kLdsLimit / (tab + (size_t)(t / G) * per) * (size_t)(t / 64);
-        if ((waves < 8 ? waves : 8) > best) {
-            best = waves < 8 ? waves : 8;
-            threads = t;
-        }
-    }
-    *lds = tab + (size_t)(threads / G) * per;
-    return *lds > kLdsLimit ? 0 : threads;
+    return group_threads(dsl_group_lds(model, K, L), dsl_G(K), lds, tab);
 }
 
 size_t draw_stats_large_workspace_bytes(int K, int Tmax, int64_t P)

@@ -297,29 +297,10 @@ static size_t estep_large_group_lds(int model, int K, int L)
     return ((2 + tabs) * G + (xl ? (size_t)K * G : 0)) * sizeof(double);
 }
 
-/* Threads per workgroup: kBlock halved down to one group until the groups'
- * LDS fits (0: one group does not), and the workgroup's LDS.  Whole
- * workgroups share a CU's LDS, so among the sizes of at least one wave the
- * one that lets the most waves (up to two per SIMD) be resident is taken, the
- * larger on a tie: with the xi rows in LDS 256 threads would hold a CU alone
- * (K = 23, L = 9: 86 KiB, four waves; 64 threads: 21.5 KiB, seven). */
+/* Threads per workgroup and its LDS: group_threads' rule (hhmm_stats.h). */
 static int estep_large_threads(int model, int K, int L, size_t *lds)
 {
-    const int G = estep_large_G(K);
-    const size_t per = estep_large_group_lds(model, K, L);
-    int threads = kBlock;
-    while (threads > G && (size_t)(threads / G) * per > kLdsLimit)
-        threads /= 2;
-    size_t best = 0;
-    for (int t = threads; t >= 64; t /= 2) {
-        const size_t waves = kLdsLimit / ((size_t)(t / G) * per) * (size_t)(t / 64);
-        if ((waves < 8 ? waves : 8) > best) {
-            best = waves < 8 ? waves : 8;
-            threads = t;
-        }
-    }
-    *lds = (size_t)(threads / G) * per;
-    return *lds > kLdsLimit ? 0 : threads;
+    return group_threads(estep_large_group_lds(model, K, L), estep_large_G(K), lds);
 }
 
 size_t estep_large_workspace_bytes(int K, int Tmax, int64_t P)

@@ -4,8 +4,9 @@
  * (hhmm_estep.hip), the draw statistics of the discrete programs and of the
  * Gaussian hmm (hhmm_draw_stats.hip), the IOHMM E-step (hhmm_estep_io.hip), the
  * pointwise predictive densities (hhmm_pointwise.hip), the E-step at
- * 8 < K <= 32 (hhmm_estep_large.hip) and the draw statistics there
- * (hhmm_draw_stats_large.hip).  The
+ * 8 < K <= 32 (hhmm_estep_large.hip), the draw statistics there
+ * (hhmm_draw_stats_large.hip) and the pointwise densities there
+ * (hhmm_pointwise_large.hip).  The
  * kernels differ; the argument checks, the DevArgs of a launch, the LDS fit,
  * the dispatch on K and the launch epilogue do not.  stats_check_tail belongs
  * to the six entries that fill an hhmm_estep_result; the IOHMM E-step and the
@@ -24,7 +25,7 @@
 
 namespace hhmm {
 
-/* Each of the eight entries gives the host path of hhmm_api.cpp (StatsEntry,
+/* Each of the nine entries gives the host path of hhmm_api.cpp (StatsEntry,
  * stats_*) a check_* and a launch_*; what those share follows them.
  *
  * Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
@@ -81,6 +82,15 @@ hhmm_status check_pointwise(const hhmm_request *r, const hhmm_pointwise_result *
 size_t pointwise_workspace_bytes(const hhmm_request *r, int64_t P);
 hhmm_status launch_pointwise(const hhmm_request *r, const hhmm_pointwise_result *res, int64_t P, void *ws,
                              hipStream_t st);
+
+/* Pointwise predictive densities at kMaxK < K <= kMaxKLarge
+ * (hhmm_pointwise_large.hip): the same three; the workspace holds l_t,
+ * [P, T_max], where the caller gives no lp_t (P * T_max * 8 bytes whatever the
+ * result holds: the size is a function of the request). */
+hhmm_status check_pointwise_large(const hhmm_request *r, const hhmm_pointwise_result *o);
+size_t pointwise_large_workspace_bytes(const hhmm_request *r, int64_t P);
+hhmm_status launch_pointwise_large(const hhmm_request *r, const hhmm_pointwise_result *res, int64_t P, void *ws,
+                                   hipStream_t st);
 
 /* Head of an entry's check_*, in this order: NULL request, ABI, model id, the
  * entry's scope (`scope` says which models it takes and where the others go),
@@ -171,6 +181,31 @@ inline DevArgs stats_dev_args(const hhmm_request *r, int64_t P, void *ws)
     a.A_ij = r->draws.A_ij;
     a.ckpt = (double *)ws;
     return a;
+}
+
+/* Threads per workgroup of a state-parallel statistics kernel (a group of G
+ * lanes per pair, `per` LDS bytes per group beside `fixed` bytes per
+ * workgroup), and the workgroup's LDS: kBlock halved down to one group until
+ * the LDS fits (0: one group does not).  Whole workgroups share a CU's LDS, so
+ * among the sizes of at least one wave the one that lets the most waves (up to
+ * two per SIMD) be resident is taken, the larger on a tie: with the large-K
+ * E-step's xi rows in LDS 256 threads would hold a CU alone (K = 23, L = 9:
+ * 86 KiB, four waves; 64 threads: 21.5 KiB, seven). */
+inline int group_threads(size_t per, int G, size_t *lds, size_t fixed = 0)
+{
+    int threads = kBlock;
+    while (threads > G && fixed + (size_t)(threads / G) * per > kLdsLimit)
+        threads /= 2;
+    size_t best = 0;
+    for (int t = threads; t >= 64; t /= 2) {
+        const size_t waves = kLdsLimit / (fixed + (size_t)(t / G) * per) * (size_t)(t / 64);
+        if ((waves < 8 ? waves : 8) > best) {
+            best = waves < 8 ? waves : 8;
+            threads = t;
+        }
+    }
+    *lds = fixed + (size_t)(threads / G) * per;
+    return *lds > kLdsLimit ? 0 : threads;
 }
 
 /* waves_that_fit and launch_status: hhmm_internal.h (the HMM family's launchers use them too).

@@ -409,4 +409,10 @@ def declare(lib):
     lib.hhmm_pointwise_device.restype = C.c_int
     lib.hhmm_pointwise.argtypes = [RP, WP]
     lib.hhmm_pointwise.restype = C.c_int
+    lib.hhmm_pointwise_large_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
+    lib.hhmm_pointwise_large_workspace_size.restype = C.c_int
+    lib.hhmm_pointwise_large_device.argtypes = [RP, WP, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.hhmm_pointwise_large_device.restype = C.c_int
+    lib.hhmm_pointwise_large.argtypes = [RP, WP]
+    lib.hhmm_pointwise_large.restype = C.c_int
     return lib

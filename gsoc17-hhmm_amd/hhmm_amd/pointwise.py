@@ -13,8 +13,10 @@ input of PSIS and leave-future-out cross-validation.
 
 l_t follows the CODED likelihood of each Stan program (hmm.stan:30, quirk Q2:
 l_1 = sum_j normal_lpdf(x_1 | mu_j, sigma_j) + log sum_k p_1k).  hmm and
-hmm-multinom at K <= 8; the masked and IOHMM programs' coded step weights are
-not predictive densities.
+hmm-multinom at K <= 32: hhmm_pointwise up to K = 8 (a lane per pair),
+hhmm_pointwise_large above (a group of 16 or 32 lanes per pair, and a second
+kernel that reduces l_t over the draws); the masked and IOHMM programs' coded
+step weights are not predictive densities.
 """
 import numpy as np
 
@@ -23,10 +25,19 @@ from .api import load_library
 
 MODELS = ("hmm", "hmm-multinom")
 HIGH_VAR = 0.4  # var_t above this: the usual WAIC reliability warning
+MAX_K_LANE = 8  # hhmm_pointwise: the lane-per-pair kernel (csrc kMaxK)
+
+
+def entry_name(K):
+    """The library entry pointwise_predictive() calls at K states: "pointwise"
+    up to MAX_K_LANE, "pointwise_large" above (K > 32 reaches the library,
+    which rejects it)."""
+    return "pointwise" if int(K) <= MAX_K_LANE else "pointwise_large"
 
 
 def tile_draws(model, K, L=0):
-    """Draws of one series that one workgroup reduces (0: the table does not fit LDS).
+    """Draws of one series that one workgroup of hhmm_pointwise (K <= 8) reduces
+    (0: the table does not fit LDS).
 
     More draws per series spread over ceil(D / tile_draws) workgroups, whose
     partials a finish kernel merges (hhmm_pointwise_workspace_size)."""
@@ -67,9 +78,10 @@ def pointwise_predictive(model, data, draws, pairing="grid", per_draw=False, dev
     variance of l_t over the draws (NaN with one draw per series); with
     `per_draw` also lp_t (P, T_max), l_t itself.  Steps t >= T[n] are NaN.  The
     draws of series n are S under "grid", S / N under "block" and 1 under "zip"
-    pairing; its pairs are consecutive."""
+    pairing; its pairs are consecutive.  K <= 32; hhmm_pointwise_large above 8."""
     lib = lib or load_library()
-    return _stats.call(lib, "pointwise", *prepare(model, data, draws, pairing, per_draw, device), return_status)
+    pr, res, out = prepare(model, data, draws, pairing, per_draw, device)
+    return _stats.call(lib, entry_name(pr.K), pr, res, out, return_status)
 
 
 def waic(stats, T=None):

@@ -41,7 +41,8 @@
  * The reduction uses no floating-point atomics and a fixed order: the same
  * request gives the same bits on every run, with and without lp_t.
  *
- * Scope: hmm and hmm-multinom at 1 <= K <= 8, every pairing, ragged T.  The
+ * Scope: hmm and hmm-multinom at 1 <= K <= 8 (9 <= K <= 32: the
+ * hhmm_pointwise_large entries at the end), every pairing, ragged T.  The
  * semisup, Tayal and IOHMM programs answer HHMM_ERR_UNSUPPORTED (their coded
  * step weights are masked or factorised: the ratio of consecutive forward sums
  * is not a predictive density), as do K > 8, HHMM_DEVICE_SET and an emission
@@ -90,6 +91,26 @@ hhmm_status hhmm_pointwise_device(const hhmm_request *req, hhmm_pointwise_result
  * and synchronises.  The per-step arrays make the round trip whole (uploaded,
  * then downloaded), so a step t >= T[n] keeps what the caller put there. */
 hhmm_status hhmm_pointwise(const hhmm_request *req, hhmm_pointwise_result *res);
+
+/* The same three at 9 <= K <= 32 (the state-parallel kernels: a group of 16
+ * lanes per pair up to K = 16, of 32 above), hmm and hmm-multinom, the same
+ * hhmm_pointwise_result with every field as above -- the layouts, the steps
+ * t >= T[n] left untouched, the IEEE rules, the coded likelihood, the same bits
+ * on every run with and without lp_t and through either entry.  K <= 8 answers
+ * HHMM_ERR_UNSUPPORTED here (hhmm_pointwise takes it), as do K > 32, the other
+ * programs, HHMM_DEVICE_SET and an emission table whose group does not fit a
+ * CU's LDS: two exchange slots and the [L][G] table, (2 + L) * G * 8 bytes
+ * against 160 KiB, i.e. L > 1278 at K <= 16 (G = 16) and L > 638 above (G = 32).
+ *
+ * Workspace: l_t itself, P * T_max * 8 bytes, which a second kernel reduces
+ * over the draws of each cell.  The size is a function of the request alone,
+ * so it is reported (and required by the device entry) whatever the result
+ * struct holds; when lp_t is given l_t goes there and the workspace is not
+ * touched. */
+hhmm_status hhmm_pointwise_large_workspace_size(const hhmm_request *req, size_t *bytes);
+hhmm_status hhmm_pointwise_large_device(const hhmm_request *req, hhmm_pointwise_result *res, void *workspace,
+                                        size_t workspace_bytes, void *stream);
+hhmm_status hhmm_pointwise_large(const hhmm_request *req, hhmm_pointwise_result *res);
 
 #ifdef __cplusplus
 }
