@@ -1735,9 +1735,9 @@ hhmm_status hhmm_extract_features(const hhmm_ticks *ticks, hhmm_legs *legs, int 
 /* ------------------------------------------------------------------ */
 /* Statistics per (series, draw) pair: the E-step (include/hhmm_estep.h), */
 /* the draw statistics (hhmm_gibbs.h, hhmm_gibbs_gauss.h), the expected  */
-/* draw statistics (hhmm_expect.h), the IOHMM E-step (hhmm_estep_io.h)  */
-/* and the pointwise predictive densities (hhmm_pointwise.h) share one  */
-/* host path                                                            */
+/* draw statistics (hhmm_expect.h), the IOHMM E-step (hhmm_estep_io.h), */
+/* the pointwise predictive densities (hhmm_pointwise.h) and PSIS-LOO / */
+/* -LFO on top of them (hhmm_psis.h) share one host path                */
 /* ------------------------------------------------------------------ */
 
 /* One array of a host call: uploaded from host_in, or downloaded to host_out
@@ -1756,6 +1756,7 @@ union StatsResult {
     hhmm_estep_result estep;
     hhmm_estep_io_result io;
     hhmm_pointwise_result pw;
+    hhmm_psis_result psis; /* psis.pw is pw */
 };
 
 /* What tells the entries apart on the host.  The result struct is the
@@ -1895,6 +1896,19 @@ static void pointwise_arrays(const StatsEntry &, const hhmm_request *req, const 
     };
 }
 
+/* hhmm_psis_result: the pointwise arrays, then three more [N, T_max] arrays that make the round trip whole */
+static void psis_arrays(const StatsEntry &en, const hhmm_request *req, const void *res_, hhmm_request *dr_,
+                        StatsResult *dq_, std::vector<StatsArr> &arrs)
+{
+    const hhmm_psis_result *res = (const hhmm_psis_result *)res_;
+    hhmm_psis_result &dq = dq_->psis;
+    pointwise_arrays(en, req, &res->pw, dr_, dq_, arrs);
+    const size_t cells = (size_t)req->data.n_series * (size_t)req->data.T_max * 8;
+    arrs.push_back({res->elpd_t, res->elpd_t, (void **)&dq.elpd_t, cells});
+    arrs.push_back({res->khat_t, res->khat_t, (void **)&dq.khat_t, cells});
+    arrs.push_back({res->neff_t, res->neff_t, (void **)&dq.neff_t, cells});
+}
+
 static size_t no_workspace(const hhmm_request *, int64_t) { return 0; }
 static size_t estep_workspace(const hhmm_request *req, int64_t P)
 {
@@ -1965,6 +1979,22 @@ static const StatsEntry kPointwiseLarge = {"large-K pointwise",
                                            kMaxK + 1,
                                            kMaxKLarge,
                                            "hhmm_pointwise"};
+static const StatsEntry kPsisLoo = {"PSIS-LOO",
+                                    false,
+                                    typed_check<hhmm_psis_result, check_psis>,
+                                    typed_launch<hhmm_psis_result, launch_psis_loo>,
+                                    psis_loo_workspace_bytes,
+                                    psis_arrays,
+                                    1,
+                                    kMaxKLarge};
+static const StatsEntry kPsisLfo = {"PSIS-LFO",
+                                    false,
+                                    typed_check<hhmm_psis_result, check_psis>,
+                                    typed_launch<hhmm_psis_result, launch_psis_lfo>,
+                                    psis_lfo_workspace_bytes,
+                                    psis_arrays,
+                                    1,
+                                    kMaxKLarge};
 static const StatsEntry kEstepIo = {"IOHMM E-step",
                                     false,
                                     typed_check<hhmm_estep_io_result, check_estep_io>,
@@ -2210,5 +2240,27 @@ hhmm_status hhmm_pointwise_large(const hhmm_request *req, hhmm_pointwise_result 
 {
     return stats_host(kPointwiseLarge, req, res);
 }
+
+hhmm_status hhmm_psis_loo_workspace_size(const hhmm_request *req, size_t *bytes)
+{
+    return stats_workspace_size(kPsisLoo, req, bytes);
+}
+hhmm_status hhmm_psis_loo_device(const hhmm_request *req, hhmm_psis_result *res, void *workspace,
+                                 size_t workspace_bytes_, void *stream)
+{
+    return stats_device(kPsisLoo, req, res, workspace, workspace_bytes_, stream);
+}
+hhmm_status hhmm_psis_loo(const hhmm_request *req, hhmm_psis_result *res) { return stats_host(kPsisLoo, req, res); }
+
+hhmm_status hhmm_psis_lfo_workspace_size(const hhmm_request *req, size_t *bytes)
+{
+    return stats_workspace_size(kPsisLfo, req, bytes);
+}
+hhmm_status hhmm_psis_lfo_device(const hhmm_request *req, hhmm_psis_result *res, void *workspace,
+                                 size_t workspace_bytes_, void *stream)
+{
+    return stats_device(kPsisLfo, req, res, workspace, workspace_bytes_, stream);
+}
+hhmm_status hhmm_psis_lfo(const hhmm_request *req, hhmm_psis_result *res) { return stats_host(kPsisLfo, req, res); }
 
 } // extern "C"

@@ -6,7 +6,8 @@
  * pointwise predictive densities (hhmm_pointwise.hip), the E-step at
  * 8 < K <= 32 (hhmm_estep_large.hip), the draw statistics there
  * (hhmm_draw_stats_large.hip) and the pointwise densities there
- * (hhmm_pointwise_large.hip).  The
+ * (hhmm_pointwise_large.hip) and PSIS-LOO / -LFO on top of both
+ * (hhmm_psis.hip).  The
  * kernels differ; the argument checks, the DevArgs of a launch, the LDS fit,
  * the dispatch on K and the launch epilogue do not.  stats_check_tail belongs
  * to the six entries that fill an hhmm_estep_result; the IOHMM E-step and the
@@ -22,10 +23,11 @@
 #include "hhmm_gibbs_gauss.h"
 #include "hhmm_internal.h"
 #include "hhmm_pointwise.h"
+#include "hhmm_psis.h"
 
 namespace hhmm {
 
-/* Each of the nine entries gives the host path of hhmm_api.cpp (StatsEntry,
+/* Each of the eleven entries gives the host path of hhmm_api.cpp (StatsEntry,
  * stats_*) a check_* and a launch_*; what those share follows them.
  *
  * Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
@@ -91,6 +93,17 @@ hhmm_status check_pointwise_large(const hhmm_request *r, const hhmm_pointwise_re
 size_t pointwise_large_workspace_bytes(const hhmm_request *r, int64_t P);
 hhmm_status launch_pointwise_large(const hhmm_request *r, const hhmm_pointwise_result *res, int64_t P, void *ws,
                                    hipStream_t st);
+
+/* PSIS-LOO and PSIS-LFO (hhmm_psis.hip) at 1 <= K <= kMaxKLarge: one check (it
+ * hands the sweep's own scope to check_pointwise or check_pointwise_large by
+ * K); the workspace is the chosen sweep's, l_t where that sweep does not keep it
+ * (K <= kMaxK) and, for LFO, the suffix sums; the launch is the sweep, the
+ * suffix kernel (LFO) and the cell kernel on `st`. */
+hhmm_status check_psis(const hhmm_request *r, const hhmm_psis_result *o);
+size_t psis_loo_workspace_bytes(const hhmm_request *r, int64_t P);
+size_t psis_lfo_workspace_bytes(const hhmm_request *r, int64_t P);
+hhmm_status launch_psis_loo(const hhmm_request *r, const hhmm_psis_result *res, int64_t P, void *ws, hipStream_t st);
+hhmm_status launch_psis_lfo(const hhmm_request *r, const hhmm_psis_result *res, int64_t P, void *ws, hipStream_t st);
 
 /* Head of an entry's check_*, in this order: NULL request, ABI, model id, the
  * entry's scope (`scope` says which models it takes and where the others go),

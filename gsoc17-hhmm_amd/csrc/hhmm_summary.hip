@@ -34,6 +34,7 @@
 
 #include "hhmm_summary.h"
 #include "hhmm_internal.h"
+#include "hhmm_sortnet.h"
 
 namespace hhmm {
 
@@ -52,45 +53,6 @@ struct SumArgs {
     int32_t n2log, G;
     double probs[HHMM_SUMMARY_MAX_PROBS + 1]; /* [Q]: argmax_prob */
 };
-
-/* LDS slot of key i: one pad key per eight, so a thread's eight consecutive
- * keys (64 B) and its neighbours' fall on different banks. */
-static __device__ __forceinline__ int sum_ph(int i) { return i + (i >> 3); }
-constexpr size_t sum_lds_bytes(size_t keys) { return sizeof(double) * (keys + (keys >> 3)); }
-
-/* Stages j = jhi, jhi/2, .. (NST of them) of phase kk of the bitonic network
- * over E keys in slots of n2: a thread takes the 2^NST keys that differ in
- * those stages' index bits, exchanges them in registers and writes them back.
- * They share the bit kk of their index, hence the direction. */
-template <int NST, int THREADS>
-static __device__ __forceinline__ void sum_pass(double *keys, int E, int n2, int kk, int jhi, int tid)
-{
-    constexpr int R = 1 << NST;
-    const int low = jhi >> (NST - 1);
-    for (int gi = tid; gi < (E >> NST); gi += THREADS) {
-        const int base = ((gi & ~(low - 1)) << NST) | (gi & (low - 1));
-        /* a descending group is the ascending network on the reversed row */
-        const int rev = ((base & (n2 - 1)) & kk) == 0 ? 0 : R - 1;
-        double r[R];
-#pragma unroll
-        for (int m = 0; m < R; ++m)
-            r[m] = keys[sum_ph(base + (m ^ rev) * low)];
-#pragma unroll
-        for (int s = 0; s < NST; ++s) {
-            const int bit = 1 << (NST - 1 - s);
-#pragma unroll
-            for (int m = 0; m < R; ++m)
-                if (!(m & bit)) {
-                    const double x = r[m], y = r[m | bit];
-                    r[m] = __builtin_fmin(x, y);
-                    r[m | bit] = __builtin_fmax(x, y);
-                }
-        }
-#pragma unroll
-        for (int m = 0; m < R; ++m)
-            keys[sum_ph(base + (m ^ rev) * low)] = r[m];
-    }
-}
 
 template <int THREADS>
 __global__ void __launch_bounds__(THREADS) summary_kernel(const SumArgs a)

@@ -16,6 +16,7 @@ from .expect import expected_stats  # noqa: F401
 from .em import baum_welch  # noqa: F401
 from .estep_io import em_io, estep_io, m_step_io, score_io  # noqa: F401
 from .pointwise import pointwise_predictive, waic  # noqa: F401
+from .psis import lfo, loo, psis_cells, psis_predictive  # noqa: F401
 from .gibbs import conditional_draw, draw_stats, gibbs, stack_chains  # noqa: F401
 from .gibbs_gauss import conditional_draw_gauss, draw_stats_gauss, gibbs_gauss, relabel_ordered  # noqa: F401
 

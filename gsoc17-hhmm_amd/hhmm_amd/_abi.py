@@ -234,6 +234,39 @@ class PointwiseResult(C.Structure):
     ]
 
 
+# include/hhmm_psis.h
+PSIS_MAX_DRAWS = 16384
+
+
+class PsisResult(C.Structure):
+    _fields_ = [
+        ("pw", PointwiseResult),
+        ("elpd_t", C.c_void_p),
+        ("khat_t", C.c_void_p),
+        ("neff_t", C.c_void_p),
+    ]
+
+
+def _embedded(name):
+    return property(lambda self: getattr(self.pw, name), lambda self, v: setattr(self.pw, name, v))
+
+
+for _name, _ctype in PointwiseResult._fields_:  # res.lpd_t is res.pw.lpd_t: the helpers of _stats set fields by name
+    setattr(PsisResult, _name, _embedded(_name))
+
+
+class PsisCellsRequest(C.Structure):
+    _fields_ = [
+        ("n_series", C.c_int64),
+        ("n_draws", C.c_int64),
+        ("T_max", C.c_int32),
+        ("reserved", C.c_int32),
+        ("T", C.c_void_p),
+        ("lr", C.c_void_p),
+        ("lp", C.c_void_p),
+    ]
+
+
 # include/hhmm_estep_io.h
 class EstepIoResult(C.Structure):
     _fields_ = [
@@ -415,4 +448,22 @@ def declare(lib):
     lib.hhmm_pointwise_large_device.restype = C.c_int
     lib.hhmm_pointwise_large.argtypes = [RP, WP]
     lib.hhmm_pointwise_large.restype = C.c_int
+    # include/hhmm_psis.h
+    if hasattr(lib, "hhmm_psis_loo"):  # absent from libraries built before PSIS (A/B variants)
+        XP = C.POINTER(PsisResult)
+        for kind in ("loo", "lfo"):
+            getattr(lib, f"hhmm_psis_{kind}_workspace_size").argtypes = [RP, C.POINTER(C.c_size_t)]
+            getattr(lib, f"hhmm_psis_{kind}_workspace_size").restype = C.c_int
+            getattr(lib, f"hhmm_psis_{kind}_device").argtypes = [RP, XP, C.c_void_p, C.c_size_t, C.c_void_p]
+            getattr(lib, f"hhmm_psis_{kind}_device").restype = C.c_int
+            getattr(lib, f"hhmm_psis_{kind}").argtypes = [RP, XP]
+            getattr(lib, f"hhmm_psis_{kind}").restype = C.c_int
+        CP = C.POINTER(PsisCellsRequest)
+        lib.hhmm_psis_cells_workspace_size.argtypes = [CP, C.POINTER(C.c_size_t)]
+        lib.hhmm_psis_cells_workspace_size.restype = C.c_int
+        lib.hhmm_psis_cells_device.argtypes = [CP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]
+        lib.hhmm_psis_cells_device.restype = C.c_int
+        lib.hhmm_psis_cells.argtypes = [CP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        lib.hhmm_psis_cells.restype = C.c_int
     return lib
