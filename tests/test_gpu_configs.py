@@ -17,7 +17,8 @@ import sys
 import numpy as np
 import pytest
 
-from hhmm_amd import _abi, synth
+from hhmm_amd import synth
+from hot_plan import SCHEDULE_FLAGS, SCHEDULE_PLAN, run_planned
 from tolerances import compare, compare_all
 
 pytestmark = pytest.mark.gpu
@@ -82,20 +83,42 @@ def test_c1_full_size(engine, oracle):
 
 # ---- C2: hmm-multinom K=4, L=9, T=1000 ---------------------------------------------------
 
-@pytest.mark.parametrize("flags", [0, _abi.FLAG_VIT_LANES, _abi.FLAG_VIT_LANES | _abi.FLAG_FUSED,
-                                   _abi.FLAG_VIT_LANES | _abi.FLAG_FB_SPLIT, _abi.FLAG_VIT_LANES | _abi.FLAG_VFB],
-                         ids=["auto", "lane", "lane-fused", "lane-split", "lane-vfb"])
-def test_c2_slice(engine, oracle, flags):
-    """A 4096-pair zip slice; `lane` forces the lane-per-pair decoder the full
-    1M-pair batch dispatches to (P >= 131072); `lane-fused` the same as the
-    one-kernel forward-backward + Viterbi sweep (HHMM_FLAG_FUSED); `lane-split`
-    as the split schedule (HHMM_FLAG_FB_SPLIT: forward launch, then backward
-    beside a Viterbi decoding the packed symbols); `lane-vfb` as the phased
-    sweep (HHMM_FLAG_VFB: the Viterbi over x, then the forward-backward over
-    its packed symbols, one kernel)."""
+C2_SLICE = [
+    # (id, flags, the plan words pinned)
+    ("auto", 0, dict(schedule="separate", fb="scan", fb_mode="GAMMA", vit="states", scan_cl="32", scan_nc="32")),
+    ("lane", SCHEDULE_FLAGS["two-kernels"], SCHEDULE_PLAN["two-kernels"]),
+    ("lane-fused", SCHEDULE_FLAGS["fused"], SCHEDULE_PLAN["fused"]),
+    ("lane-split", SCHEDULE_FLAGS["split"], SCHEDULE_PLAN["split"]),
+    ("lane-vfb", SCHEDULE_FLAGS["phased"], SCHEDULE_PLAN["phased"]),
+]
+
+
+@pytest.fixture(scope="module")
+def c2_slice(oracle):
+    """The slice and the oracle's outputs: computed once, shared by the five schedules and only read."""
     data, draws = synth.hmm_multinom(N=4096, S=4096, T=1000, K=4, L=9)
-    got, ref = gpu_and_oracle(engine, oracle, "hmm-multinom", data, draws, HOT, pairing="zip", flags=flags)
-    compare_all(got, ref, HOT + ["pair_status"])
+    ref = oracle.gqs("hmm-multinom", data, draws, pars=HOT, pairing="zip", return_status=True, nthreads=threads())
+    return data, draws, ref
+
+
+@pytest.mark.parametrize("flags,plan", [c[1:] for c in C2_SLICE], ids=[c[0] for c in C2_SLICE])
+def test_c2_slice(engine, oracle, c2_slice, flags, plan):
+    """A 4096-pair zip slice at T = 1000, every schedule pinned to its plan
+    (tests/hot_plan.py).  `auto`: what a batch this small dispatches to by
+    itself, the parallel scan over T and the state-parallel decoder.  The four
+    forced ids set HHMM_FLAG_SCAN_OFF | HHMM_FLAG_VIT_SCAN_OFF beside
+    HHMM_FLAG_VIT_LANES -- without SCAN_OFF a batch of under 16384 pairs at
+    T >= 256 runs the T-scan whatever the schedule flag says -- and so reach
+    the sequential sweeps of the full 1M-pair batch: `lane` fb_kernel
+    (GAMMA|PACK|BIG) beside the lane-per-pair viterbi_kernel (HHMM_FLAG_VFB_OFF,
+    the phased sweep being the default of this request), `lane-fused` the
+    one-kernel forward-backward + Viterbi sweep (HHMM_FLAG_FUSED), `lane-split`
+    the split schedule (HHMM_FLAG_FB_SPLIT: forward launch, then backward
+    beside a Viterbi decoding the packed symbols), `lane-vfb` the phased sweep
+    (HHMM_FLAG_VFB: the Viterbi over x, then the forward-backward over its
+    packed symbols, one kernel)."""
+    data, draws, ref = c2_slice
+    run_planned(engine, oracle, "hmm-multinom", data, draws, HOT, flags, "zip", plan, ref=ref)
 
 
 def _bench_module():

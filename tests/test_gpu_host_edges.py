@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from hhmm_amd import _abi, synth
+from hot_plan import SCHEDULE_PLAN, assert_plan
 from test_gpu_host_pipeline import _dev, _host
 from test_gpu_invalid_data import C2_PARS
 from test_gpu_parity import DEVICE_MODELS
@@ -104,15 +105,19 @@ def test_one_pair_every_model(engine, oracle, model, T):
 # batch on the lane-per-pair kernels, whose last wave is the padded one: the phased sweep (vfb_kernel,
 # launched per wave) and fb_kernel beside viterbi_kernel.
 _LANES = _abi.FLAG_SCAN_OFF | _abi.FLAG_VIT_SCAN_OFF | _abi.FLAG_VIT_LANES
-WAVE_SCHEDULES = [("default", 0), ("vfb-off", _abi.FLAG_VFB_OFF), ("lanes-phased-sweep", _LANES),
-                  ("lanes-two-kernels", _LANES | _abi.FLAG_VFB_OFF)]
+_STATES = dict(schedule="separate", fb="linear", fb_mode="GAMMA|PACK|BIG", vit="states")
+# (id, flags, the plan words asserted before the run)
+WAVE_SCHEDULES = [("default", 0, _STATES), ("vfb-off", _abi.FLAG_VFB_OFF, _STATES),
+                  ("lanes-phased-sweep", _LANES, SCHEDULE_PLAN["phased"]),
+                  ("lanes-two-kernels", _LANES | _abi.FLAG_VFB_OFF, SCHEDULE_PLAN["two-kernels"])]
 
 
-@pytest.mark.parametrize("flags", [f for _, f in WAVE_SCHEDULES], ids=[i for i, _ in WAVE_SCHEDULES])
+@pytest.mark.parametrize("flags,plan", [s[1:] for s in WAVE_SCHEDULES], ids=[s[0] for s in WAVE_SCHEDULES])
 @pytest.mark.parametrize("P", [63, 64, 65])
-def test_padded_final_wave(engine, oracle, P, flags):
+def test_padded_final_wave(engine, oracle, P, flags, plan):
     import hhmm_amd
     data, draws = synth.hmm_multinom(N=P, S=P, T=64, K=4, L=9)
+    assert_plan(engine, "hmm-multinom", data, draws, C2_PARS, flags, "zip", plan)
     got = hhmm_amd.gqs("hmm-multinom", data, draws, pars=C2_PARS, pairing="zip", lib=engine, return_status=True,
                        flags=flags)
     ref = oracle.gqs("hmm-multinom", data, draws, pars=C2_PARS, pairing="zip", return_status=True)

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from hhmm_amd import _abi, synth
+from hot_plan import SCHEDULE_PLAN, assert_plan
 from tolerances import compare
 
 pytestmark = pytest.mark.gpu
@@ -52,19 +53,35 @@ def _corrupt(data, key, n, t, v):
 C2_PARS = ["loglik", "gamma_tk", "zstar_t", "logp_zstar"]
 
 
-@pytest.mark.parametrize("flags", [0, _abi.FLAG_VFB_OFF, _abi.FLAG_FUSED | _abi.FLAG_VIT_LANES,
-                                   _abi.FLAG_FB_SPLIT | _abi.FLAG_VIT_LANES],
-                         ids=["phased-sweep", "two-kernels", "fused", "split"])
-def test_multinom_symbol_out_of_range(engine, oracle, flags):
-    """C2's profile: the phased sweep checks x while it packs the symbols; with it off,
-    the separate check pass does.  The fused sweep (the plan's checked_inline = 0: the
-    check pass runs) and the split schedule (1: its forward launch checks x) at the same
-    shape; VIT_LANES keeps this batch of under 131072 pairs off the state-parallel
-    decoder, which would take it off both."""
+_STATES = dict(schedule="separate", fb="linear", fb_mode="GAMMA|PACK|BIG", vit="states", checked_inline="1")
+C2_ROWS = [
+    # (id, flags, the plan words pinned).  512 pairs at K = 4 decode state-parallel (use_vit_states: P < 131072)
+    # whatever HHMM_FLAG_VFB / VFB_OFF say, so the first two rows are fb_kernel (which checks x inline) beside
+    # viterbi_sp_kernel; HHMM_FLAG_VIT_LANES puts the batch on the lane-per-pair schedules of the full C2 batch.
+    ("default-dispatch", 0, _STATES),
+    ("two-kernels", _abi.FLAG_VFB_OFF, _STATES),
+    ("fused", _abi.FLAG_FUSED | _abi.FLAG_VIT_LANES, dict(SCHEDULE_PLAN["fused"], checked_inline="0")),
+    ("split", _abi.FLAG_FB_SPLIT | _abi.FLAG_VIT_LANES, dict(SCHEDULE_PLAN["split"], checked_inline="1")),
+    ("lanes-phased-sweep", _abi.FLAG_VIT_LANES, dict(SCHEDULE_PLAN["phased"], checked_inline="1")),
+    ("lanes-two-kernels", _abi.FLAG_VIT_LANES | _abi.FLAG_VFB_OFF,
+     dict(SCHEDULE_PLAN["two-kernels"], checked_inline="1")),
+]
+
+
+@pytest.mark.parametrize("flags,plan", [r[1:] for r in C2_ROWS], ids=[r[0] for r in C2_ROWS])
+def test_multinom_symbol_out_of_range(engine, oracle, flags, plan):
+    """C2's request at 512 pairs x T = 200, each row pinned to its plan (tests/hot_plan.py).
+    Without flags, and with the phased sweep switched off, this batch runs fb_kernel, which
+    checks x as it packs the symbols, beside the state-parallel decoder.  With VIT_LANES it
+    runs the schedules of the full batch: the phased sweep (phase 1 checks x while it packs),
+    fb_kernel beside viterbi_kernel (both check inline), the fused sweep (the plan's
+    checked_inline = 0: the check pass runs) and the split schedule (1: its forward launch
+    checks x)."""
     data, draws = synth.hmm_multinom(N=512, S=512, T=200, K=4, L=9)
     bad = _corrupt(data, "x", 37, 101, 10)       # L + 1
     bad = _corrupt(bad, "x", 200, 0, 0)          # below 1
     bad = _corrupt(bad, "x", 311, 199, -7)
+    assert_plan(engine, "hmm-multinom", data, draws, C2_PARS, flags, "zip", plan)
     _run(engine, oracle, "hmm-multinom", data, bad, draws, C2_PARS, [37, 200, 311], pairing="zip", flags=flags)
 
 
@@ -118,28 +135,34 @@ def test_large_k_symbol_out_of_range(engine, oracle):
 
 
 _LANES = _abi.FLAG_SCAN_OFF | _abi.FLAG_VIT_SCAN_OFF | _abi.FLAG_VIT_LANES
+def _sep(fb, mode, vit, inline):
+    return dict(schedule="separate", fb=fb, fb_mode=mode, vit=vit, checked_inline=inline)
+
+
 SCHEDULES = [
-    # (id, outputs, flags): which kernels read x, hence which check runs
-    ("fb", ["loglik", "gamma_tk"], _LANES),                         # fb_kernel, inline
-    ("forward", ["loglik"], _LANES),                                # fb_kernel forward only, inline
-    ("alpha-beta", ["alpha_tk", "beta_tk"], _LANES),                # fb_kernel FB_FULL, inline
-    ("log-space", ["unalpha_tk"], _LANES),                          # fb_log_kernel: check pass
-    ("viterbi", ["zstar_t", "logp_zstar"], _LANES),                 # viterbi_kernel, inline
-    ("viterbi-states", ["zstar_t"], _abi.FLAG_VIT_STATES),          # viterbi_sp_kernel: check pass
-    ("two", C2_PARS, _LANES | _abi.FLAG_VFB_OFF),                   # both inline, two streams
-    ("split", C2_PARS, _LANES | _abi.FLAG_FB_SPLIT),                # forward launch inline
-    ("fused", C2_PARS, _LANES | _abi.FLAG_FUSED),                   # fbv_kernel: check pass
-    ("scan", ["loglik", "gamma_tk"], _abi.FLAG_SCAN_FORCE),         # T-scan: check pass
+    # (id, outputs, flags, the plan words pinned): which kernels read x, hence which check runs
+    ("fb", ["loglik", "gamma_tk"], _LANES, _sep("linear", "GAMMA|PACK|BIG", "none", "1")),     # fb_kernel, inline
+    ("forward", ["loglik"], _LANES, _sep("linear", "FWD", "none", "1")),           # fb_kernel forward only, inline
+    ("alpha-beta", ["alpha_tk", "beta_tk"], _LANES, _sep("linear", "FULL", "none", "1")),  # fb_kernel FB_FULL, inline
+    ("log-space", ["unalpha_tk"], _LANES, _sep("log", "FWD", "none", "0")),        # fb_log_kernel: check pass
+    ("viterbi", ["zstar_t", "logp_zstar"], _LANES, _sep("none", "-", "lanes", "1")),    # viterbi_kernel, inline
+    ("viterbi-states", ["zstar_t"], _abi.FLAG_VIT_STATES, _sep("none", "-", "states", "0")),  # viterbi_sp_kernel: pass
+    ("two", C2_PARS, _LANES | _abi.FLAG_VFB_OFF,                                   # both inline, two streams
+     dict(SCHEDULE_PLAN["two-kernels"], checked_inline="1", side_stream="1")),
+    ("split", C2_PARS, _LANES | _abi.FLAG_FB_SPLIT, dict(SCHEDULE_PLAN["split"], checked_inline="1")),  # forward launch
+    ("fused", C2_PARS, _LANES | _abi.FLAG_FUSED, dict(SCHEDULE_PLAN["fused"], checked_inline="0")),     # check pass
+    ("scan", ["loglik", "gamma_tk"], _abi.FLAG_SCAN_FORCE,                         # T-scan: check pass
+     dict(_sep("scan", "GAMMA", "none", "0"), scan_cl="64", scan_nc="4")),
 ]
 
 
-@pytest.mark.parametrize("outs,flags", [s[1:] for s in SCHEDULES], ids=[s[0] for s in SCHEDULES])
-def test_multinom_schedules_ragged(engine, oracle, outs, flags):
+@pytest.mark.parametrize("outs,flags,plan", [s[1:] for s in SCHEDULES], ids=[s[0] for s in SCHEDULES])
+def test_multinom_schedules_ragged(engine, oracle, outs, flags, plan):
     """Every schedule of the hmm-multinom request flags the same series: the sweeps
     that read x over whole series check it inline (fb_sweep, viterbi_block, the phased
     sweep), the others leave it to data_check_kernel.  Ragged lengths put violations
     in a wave's full chunks, in its partial chunks, and in the padding past a
-    series' own length (not a violation)."""
+    series' own length (not a violation).  Each row asserts its plan first."""
     N, T = 300, 203
     data, draws = synth.hmm_multinom(N=N, S=N, T=T, K=4, L=9, seed=11)
     rng = np.random.default_rng(5)
@@ -154,6 +177,7 @@ def test_multinom_schedules_ragged(engine, oracle, outs, flags):
     bad = _corrupt(bad, "x", 29, 170, 0)          # t = T[29]: padding, not a violation
     bad = _corrupt(bad, "x", 41, 100, -3)
     bad = _corrupt(bad, "x", 299, 149, 12)        # the last pair (the final wave's padded lanes)
+    assert_plan(engine, "hmm-multinom", data, draws, outs, flags, "zip", plan)
     _run(engine, oracle, "hmm-multinom", data, bad, draws, outs, [5, 17, 41, 60, 299], pairing="zip", flags=flags)
 
 
@@ -162,13 +186,14 @@ INT32_MIN, INT32_MAX = -2 ** 31, 2 ** 31 - 1
 # state-parallel instead (use_vit_states) and the request falls back to fb_kernel + viterbi_sp_kernel, so
 # FLAG_VIT_LANES (_LANES) is what puts this small batch on it; the default dispatch runs beside it.
 EXTREME_SCHEDULES = [s for s in SCHEDULES if s[0] in ("fb", "log-space")] + [
-    ("phased-sweep", C2_PARS, _LANES),                              # vfb_kernel: inline, while it packs x
-    ("default-dispatch", C2_PARS, 0),                               # fb_kernel inline + viterbi_sp_kernel
+    ("phased-sweep", C2_PARS, _LANES, dict(SCHEDULE_PLAN["phased"], checked_inline="1")),  # vfb_kernel: inline
+    ("default-dispatch", C2_PARS, 0, _STATES),                      # fb_kernel inline + viterbi_sp_kernel
 ]
 
 
-@pytest.mark.parametrize("outs,flags", [s[1:] for s in EXTREME_SCHEDULES], ids=[s[0] for s in EXTREME_SCHEDULES])
-def test_multinom_extreme_symbols(engine, oracle, outs, flags):
+@pytest.mark.parametrize("outs,flags,plan", [s[1:] for s in EXTREME_SCHEDULES],
+                         ids=[s[0] for s in EXTREME_SCHEDULES])
+def test_multinom_extreme_symbols(engine, oracle, outs, flags, plan):
     """The ends of int32 on the three checks that differ (inline in fb_sweep, the
     separate check pass, inline in the phased sweep, whose 4-bit packed symbols
     then feed its other phases) and on the default dispatch of this batch:
@@ -184,6 +209,7 @@ def test_multinom_extreme_symbols(engine, oracle, outs, flags):
     bad = _corrupt(data, "x", 3, 0, INT32_MIN)            # step 0 (the init row)
     bad = _corrupt(bad, "x", 70, 54, INT32_MAX)           # the series' last valid step
     bad = _corrupt(bad, "x", 129, 41, INT32_MIN)          # t = T[129]: padding, in the final (two-lane) wave
+    assert_plan(engine, "hmm-multinom", data, draws, outs, flags, "zip", plan)
     _run(engine, oracle, "hmm-multinom", data, bad, draws, outs, [3, 70], pairing="zip", flags=flags)
 
 

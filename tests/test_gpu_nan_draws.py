@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from hhmm_amd import _abi, synth
+from hot_plan import SCHEDULE_PLAN, assert_plan
 from tolerances import compare_all
 
 pytestmark = pytest.mark.gpu
@@ -29,38 +30,47 @@ N, S, T, SPOILED = 2, 64, 60, 5
 
 MULTINOM4 = ("hmm-multinom", (("K", 4), ("L", 9)))
 _LANES = _abi.FLAG_SCAN_OFF | _abi.FLAG_VIT_SCAN_OFF | _abi.FLAG_VIT_LANES
+def _plan(schedule="separate", fb="linear", fb_mode="GAMMA", vit="lanes", **more):
+    return dict(schedule=schedule, fb=fb, fb_mode=fb_mode, vit=vit, **more)
+
+
+_BIG = "GAMMA|PACK|BIG"
+_NONE = dict(schedule="none")    # not an HMM-family request at K <= 8: no plan (hhmm_large.h, hhmm_iohmm.h)
 PATHS = [
-    # (id, (model, sizes), flags)
+    # (id, (model, sizes), flags, the plan words the request must give: asserted before the run)
     # At K <= 4 a batch this small decodes state-parallel (use_vit_states: P < 131072): these five rows
     # share viterbi_sp_kernel and differ in the forward-backward half (fb_kernel on its own or beside the
     # decoder, its forward launch alone, the T-scan).
-    ("multinom-states-default", MULTINOM4, 0),
-    ("multinom-states-vfb-off", MULTINOM4, _abi.FLAG_VFB_OFF),
-    ("multinom-states-fb-split", MULTINOM4, _abi.FLAG_FB_SPLIT),
-    ("multinom-states-forced", MULTINOM4, _abi.FLAG_VIT_STATES),
-    ("multinom-states-tscan", MULTINOM4, _abi.FLAG_SCAN_FORCE),
-    ("hmm-K3", ("hmm", (("K", 3),)), 0),
-    ("multinom-K12", ("hmm-multinom", (("K", 12), ("L", 9))), 0),
-    ("iohmm-reg-K3", ("iohmm-reg", (("K", 3),)), 0),
+    ("multinom-states-default", MULTINOM4, 0, _plan(fb_mode=_BIG, vit="states")),
+    ("multinom-states-vfb-off", MULTINOM4, _abi.FLAG_VFB_OFF, _plan(fb_mode=_BIG, vit="states")),
+    ("multinom-states-fb-split", MULTINOM4, _abi.FLAG_FB_SPLIT, _plan(fb_mode=_BIG, vit="states")),
+    ("multinom-states-forced", MULTINOM4, _abi.FLAG_VIT_STATES, _plan(fb_mode=_BIG, vit="states")),
+    ("multinom-states-tscan", MULTINOM4, _abi.FLAG_SCAN_FORCE, _plan(fb="scan", vit="states", scan_nc="1")),
+    ("hmm-K3", ("hmm", (("K", 3),)), 0, _plan(vit="states")),
+    ("multinom-K12", ("hmm-multinom", (("K", 12), ("L", 9))), 0, _NONE),
+    ("iohmm-reg-K3", ("iohmm-reg", (("K", 3),)), 0, _NONE),
     # The rows above never reach the lane-per-pair recursions that the large batches run (vit_step: the
     # phased sweep, viterbi_kernel, the split and the fused sweeps).  FLAG_VIT_LANES puts this batch on
     # them; K = 6 takes them by default.
-    ("multinom-lanes-phased", MULTINOM4, _LANES),
-    ("multinom-lanes-two-kernels", MULTINOM4, _LANES | _abi.FLAG_VFB_OFF),
-    ("multinom-lanes-fb-split", MULTINOM4, _LANES | _abi.FLAG_FB_SPLIT),
-    ("multinom-lanes-fused", MULTINOM4, _LANES | _abi.FLAG_FUSED),
-    ("hmm-K3-lanes", ("hmm", (("K", 3),)), _LANES),
-    ("multinom-K6", ("hmm-multinom", (("K", 6), ("L", 9))), 0),
-    ("iohmm-reg-K3-lanes", ("iohmm-reg", (("K", 3),)), _LANES),
-    ("tayal-lanes", ("hhmm-tayal2009", (("K", 4),)), _LANES),
+    ("multinom-lanes-phased", MULTINOM4, _LANES, SCHEDULE_PLAN["phased"]),
+    ("multinom-lanes-two-kernels", MULTINOM4, _LANES | _abi.FLAG_VFB_OFF, SCHEDULE_PLAN["two-kernels"]),
+    ("multinom-lanes-fb-split", MULTINOM4, _LANES | _abi.FLAG_FB_SPLIT, SCHEDULE_PLAN["split"]),
+    ("multinom-lanes-fused", MULTINOM4, _LANES | _abi.FLAG_FUSED, SCHEDULE_PLAN["fused"]),
+    ("hmm-K3-lanes", ("hmm", (("K", 3),)), _LANES, _plan()),
+    ("multinom-K6", ("hmm-multinom", (("K", 6), ("L", 9))), 0, _plan(fb_mode="GAMMA|PACK")),
+    ("iohmm-reg-K3-lanes", ("iohmm-reg", (("K", 3),)), _LANES, _NONE),
+    ("tayal-lanes", ("hhmm-tayal2009", (("K", 4),)), _LANES, _plan()),
     # the T-parallel exact decoder (hhmm_vscan.h: chosen by itself for few long series), forced below its
     # automatic range.  Its chunk 0 runs the step decoder and T = 60 is one chunk of 512 steps, so the
-    # T = 1100 rows add the chunk products, the tie grid and the chunk-parallel back-trace (3 chunks).
-    ("multinom-vit-scan", MULTINOM4, _abi.FLAG_VIT_SCAN),
-    ("hmm-K4-vit-scan", ("hmm", (("K", 4),)), _abi.FLAG_VIT_SCAN),
-    ("tayal-vit-scan", ("hhmm-tayal2009", (("K", 4),)), _abi.FLAG_VIT_SCAN),
-    ("multinom-vit-scan-T1100", ("hmm-multinom", (("K", 4), ("L", 9), ("T", 1100))), _abi.FLAG_VIT_SCAN),
-    ("hmm-K4-vit-scan-T1100", ("hmm", (("K", 4), ("T", 1100))), _abi.FLAG_VIT_SCAN),
+    # T = 1100 rows add the chunk products, the tie grid and the chunk-parallel back-trace (3 chunks);
+    # at T = 1100 >= 256 the forward-backward beside it is the T-scan.
+    ("multinom-vit-scan", MULTINOM4, _abi.FLAG_VIT_SCAN, _plan(fb_mode=_BIG, vit="vscan", vs_nc="1")),
+    ("hmm-K4-vit-scan", ("hmm", (("K", 4),)), _abi.FLAG_VIT_SCAN, _plan(vit="vscan", vs_nc="1")),
+    ("tayal-vit-scan", ("hhmm-tayal2009", (("K", 4),)), _abi.FLAG_VIT_SCAN, _plan(vit="vscan", vs_nc="1")),
+    ("multinom-vit-scan-T1100", ("hmm-multinom", (("K", 4), ("L", 9), ("T", 1100))), _abi.FLAG_VIT_SCAN,
+     _plan(fb="scan", vit="vscan", vs_nc="3")),
+    ("hmm-K4-vit-scan-T1100", ("hmm", (("K", 4), ("T", 1100))), _abi.FLAG_VIT_SCAN,
+     _plan(fb="scan", vit="vscan", vs_nc="3")),
 ]
 
 # Seeds at which the oracle's path of the spoiled draw enters column j from
@@ -94,7 +104,8 @@ def _kinds(model, K):
     return [f"A-0-{j}" for j in range(K)] + ["A-last-0", "emission", "p1"]
 
 
-CASES = [(pid, mk, flags, kind) for pid, mk, flags in PATHS for kind in _kinds(mk[0], dict(mk[1])["K"])]
+CASES = [(pid, mk, flags, kind) for pid, mk, flags, _ in PATHS for kind in _kinds(mk[0], dict(mk[1])["K"])]
+PLANS = {pid: plan for pid, _, _, plan in PATHS}
 
 
 @functools.lru_cache(maxsize=None)
@@ -145,7 +156,8 @@ def test_nan_draw_matches_oracle(engine, oracle, pid, mk, flags, kind):
     # the NaN stays in its draw: every other pair is an ordinary one
     others = np.setdiff1d(np.arange(N * S), spoiled)
     assert np.isfinite(ref["loglik"][others]).all() and np.isnan(ref["loglik"][spoiled]).all()
-    got = hhmm_amd.gqs(model, data, draws, pars=PARS, lib=engine, return_status=True, flags=flags)
+    assert_plan(engine, model, data, draws, PARS, flags, "grid", PLANS[pid])
+    got =hhmm_amd.gqs(model, data, draws, pars=PARS, lib=engine, return_status=True, flags=flags)
     # Tayal's gamma has a comparison of its own (Q6: tests/test_gpu_configs.py compare_tayal_gamma)
     names = [n for n in PARS if not (model == "hhmm-tayal2009" and n == "gamma_tk")]
     compare_all(got, ref, names + ["pair_status"])

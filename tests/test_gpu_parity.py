@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from hhmm_amd import _abi, synth
+from hot_plan import SCHEDULE_FLAGS, SCHEDULE_PLAN, run_planned
 from tolerances import compare, compare_all
 
 pytestmark = pytest.mark.gpu
@@ -253,15 +254,13 @@ def test_split_schedule(engine, oracle, T, sched):
     backward launch -- bit-exact paths, gamma / loglik within tolerance, at
     series lengths around the 8-step chunk and 16-step block sizes.  `vfb`:
     the phased sweep (HHMM_FLAG_VFB), whose Viterbi packs the symbols its
-    forward-backward reads."""
-    import hhmm_amd
+    forward-backward reads.  T < 256 keeps this batch off the T-scan, and the
+    plan is asserted: `split` / `phased` (tests/hot_plan.py)."""
     pars = ["loglik", "gamma_tk", "zstar_t", "logp_zstar"]
     data, draws = synth.hmm_multinom(N=70, S=70, T=T, K=4, L=9)
     flags = _abi.FLAG_VIT_LANES | (_abi.FLAG_FB_SPLIT if sched == "split" else _abi.FLAG_VFB)
-    got = hhmm_amd.gqs("hmm-multinom", data, draws, pars=pars, lib=engine, flags=flags, pairing="zip",
-                       return_status=True)
-    ref = oracle.gqs("hmm-multinom", data, draws, pars=pars, pairing="zip", return_status=True)
-    compare_all(got, ref, pars + ["pair_status"])
+    run_planned(engine, oracle, "hmm-multinom", data, draws, pars, flags, "zip",
+                SCHEDULE_PLAN["split" if sched == "split" else "phased"], nthreads=1)
 
 
 @pytest.mark.parametrize("scale", [1.0, 8.0, 40.0, 400.0])
@@ -300,10 +299,12 @@ def _near_impossible_runs(tiny, K=4, N=192, which=(70,)):
 
 
 @pytest.mark.parametrize("tiny", [1e-30, 1e-70, 1e-90, 1e-200])
-@pytest.mark.parametrize("flags", [_abi.FLAG_VIT_LANES, _abi.FLAG_VIT_LANES | _abi.FLAG_FUSED,
-                                   _abi.FLAG_VIT_LANES | _abi.FLAG_FB_SPLIT, _abi.FLAG_VIT_LANES | _abi.FLAG_VFB],
+@pytest.mark.parametrize("flags,sched", [(_abi.FLAG_VIT_LANES, "phased"),
+                                         (_abi.FLAG_VIT_LANES | _abi.FLAG_FUSED, "fused"),
+                                         (_abi.FLAG_VIT_LANES | _abi.FLAG_FB_SPLIT, "split"),
+                                         (_abi.FLAG_VIT_LANES | _abi.FLAG_VFB, "phased")],
                          ids=["default", "fused", "split", "vfb"])
-def test_gamma_profile_near_impossible_runs(engine, oracle, tiny, flags):
+def test_gamma_profile_near_impossible_runs(engine, oracle, tiny, flags, sched):
     """The gamma profile renormalises every 4 steps (FB_BIG, kBigRenorm) only
     in waves whose pairs bound the 4-step shrink (renorm_sparse_safe: the
     smallest emission times the smallest row / column max of A >= 2^-39);
@@ -312,14 +313,12 @@ def test_gamma_profile_near_impossible_runs(engine, oracle, tiny, flags):
     ~1e-300 per step like the reference's log space.  Every schedule of the
     C2 request (the bench's lane decoder, the fused sweep, the split
     launches), against the oracle, with the safe and the dense waves in one
-    batch."""
-    import hhmm_amd
+    batch.  T = 200 < 256 keeps the batch off the T-scan; the plan is asserted:
+    `default` (HHMM_FLAG_VIT_LANES alone) is the phased sweep, like `vfb`."""
     pars = ["loglik", "gamma_tk", "zstar_t", "logp_zstar"]
     data, draws = _near_impossible_runs(tiny)
-    got = hhmm_amd.gqs("hmm-multinom", data, draws, pars=pars, lib=engine, pairing="zip", flags=flags,
-                       return_status=True)
-    ref = oracle.gqs("hmm-multinom", data, draws, pars=pars, pairing="zip", return_status=True)
-    compare_all(got, ref, pars + ["pair_status"])
+    got, _ = run_planned(engine, oracle, "hmm-multinom", data, draws, pars, flags, "zip", SCHEDULE_PLAN[sched],
+                         nthreads=1)
     assert np.isfinite(got["loglik"]).all()
 
 
@@ -361,17 +360,17 @@ def test_unsupported_shape_leaves_no_kernel_running(engine, oracle):
 @pytest.mark.parametrize("sched", ["split", "vfb"])
 def test_split_schedule_ragged(engine, oracle, sched):
     """Ragged lengths inside one wave: a lane's packed rows past its own end
-    are padding the decoder never consumes."""
-    import hhmm_amd
+    are padding the decoder never consumes.  T_max = 300 >= 256 would send
+    this batch to the T-scan whatever the schedule flag, so the request sets
+    HHMM_FLAG_SCAN_OFF | HHMM_FLAG_VIT_SCAN_OFF as well and asserts its plan:
+    the split launches and the phased sweep are what runs."""
     pars = ["loglik", "gamma_tk", "zstar_t", "logp_zstar"]
     N = 130
     data, draws = synth.hmm_multinom(N=N, S=N, T=300, K=4, L=9)
     data["T"] = np.random.default_rng(5).integers(1, 301, N).astype(np.int32)
-    flags = _abi.FLAG_VIT_LANES | (_abi.FLAG_FB_SPLIT if sched == "split" else _abi.FLAG_VFB)
-    got = hhmm_amd.gqs("hmm-multinom", data, draws, pars=pars, lib=engine, flags=flags, pairing="zip",
-                       return_status=True)
-    ref = oracle.gqs("hmm-multinom", data, draws, pars=pars, pairing="zip", return_status=True)
-    compare_all(got, ref, pars + ["pair_status"])
+    sched = "split" if sched == "split" else "phased"
+    run_planned(engine, oracle, "hmm-multinom", data, draws, pars, SCHEDULE_FLAGS[sched], "zip", SCHEDULE_PLAN[sched],
+                nthreads=1)
 
 
 @pytest.mark.parametrize("model", ["hmm-multinom", "hhmm-tayal2009"])
@@ -393,8 +392,10 @@ def test_vfb_invalid_backpointer(engine, oracle):
     """The phased sweep (HHMM_FLAG_VFB) on the all -inf delta_T pair: flagged,
     the path zeroed, gamma / loglik as the oracle; with a near-impossible
     symbol in another pair of the wave, so the wave takes the per-step
-    renormalisation kernel (zstar_T parked in zstar[T-1])."""
+    renormalisation kernel (zstar_T parked in zstar[T-1]).  The plan is
+    asserted: `phased`."""
     import hhmm_amd
+    from hot_plan import assert_plan
     pars = ["loglik", "gamma_tk", "zstar_t", "logp_zstar"]
     data, draws = synth.hmm_multinom(N=3, S=3, T=40, K=4, L=9)
     draws["phi_k"][0, :, 8] = 0.0
@@ -403,6 +404,7 @@ def test_vfb_invalid_backpointer(engine, oracle):
     data["x"][0, 7] = 9
     data["x"][2, 10:20] = 8
     for flags in (_abi.FLAG_VIT_LANES | _abi.FLAG_VFB,):
+        assert_plan(engine, "hmm-multinom", data, draws, pars, flags, "zip", SCHEDULE_PLAN["phased"])
         got = hhmm_amd.gqs("hmm-multinom", data, draws, pars=pars, lib=engine, flags=flags, pairing="zip",
                            return_status=True)
         ref = oracle.gqs("hmm-multinom", data, draws, pars=pars, pairing="zip", return_status=True)

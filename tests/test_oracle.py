@@ -118,6 +118,15 @@ def test_kat_viterbi_init_quirk_and_t1(oracle):
     assert np.all(out["zstar_t"][:, 0] == 4)
 
 
+def test_pair_status_is_the_requested_viterbi_s(oracle):
+    """pair_status reports the Viterbi backtrack (include/hhmm.h).  K = 3 at T = 1 fails it (above); a
+    request for neither zstar_t nor logp_zstar decodes no path, as the library does not, and reports 0."""
+    data, draws = synth.hmm_multinom(N=1, S=2, T=1, K=3, L=5)
+    for pars, want in ((["loglik", "gamma_tk"], 0), (["gamma_tk", "logp_zstar"], 1), (["zstar_t"], 1)):
+        out = oracle.gqs("hmm-multinom", data, draws, pars=pars, return_status=True)
+        assert np.all(out["pair_status"] == want) and out["status"] == want, pars
+
+
 def test_kat_unbeta_offset(oracle):
     """Q1: unbeta_tk[T] = 1, and every unbeta carries the +1 offset."""
     data, draws = synth.hmm_multinom(N=1, S=2, T=10, K=3, L=5)
