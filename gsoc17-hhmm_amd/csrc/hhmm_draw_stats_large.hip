@@ -52,11 +52,6 @@ namespace hhmm {
 /* the det exp's 2^(j/128) table, copied to LDS once per workgroup (hmm) */
 constexpr size_t kDslTabBytes = 128 * sizeof(hhmm_exp2_entry);
 
-struct DrawStatsLargeOut {
-    double *loglik, *n1, *xi, *c, *w, *s1, *s2;
-    int32_t *status;
-};
-
 /* lkf_emit (hhmm_large.h) with the group max it subtracts handed back: the same
  * operations on the same values, so the same bits. */
 template <int MODEL, int G, int KM>
@@ -73,7 +68,7 @@ __device__ __forceinline__ double dsl_emit(const LkLane<MODEL, G, KM> &ln, int x
 }
 
 template <int MODEL, int G, int KM>
-__global__ void __launch_bounds__(kBlock) draw_stats_large_kernel(const DevArgs a, const DrawStatsLargeOut o)
+__global__ void __launch_bounds__(kBlock) draw_stats_large_kernel(const DevArgs a, const LkStatsOut o)
 {
     HIP_DYNAMIC_SHARED(double, lds)
     constexpr bool GAUSS = LkTraits<MODEL>::kGauss;
@@ -108,15 +103,8 @@ __global__ void __launch_bounds__(kBlock) draw_stats_large_kernel(const DevArgs 
         __syncthreads();
 
     auto ckpt = [&](int c) -> double & { return a.ckpt[q + a.P * ((int64_t)c * K + (ln.on ? ln.j : 0))]; };
-    /* the data check rides on the forward sweep's loads: lane j of the group
-     * tests the symbol of step b * G + j (steps of the series only) */
-    bool xbad = false;
-    auto block = [&](int b) {
-        const LkObs<MODEL, G> ob = lk_block<MODEL, G, KM>(ln, a, b);
-        if constexpr (!GAUSS)
-            xbad |= (b * G + ln.j < Tp) & ((ob.x < 1) | (ob.x > L));
-        return ob;
-    };
+    bool xbad = false; /* the data check rides on the forward sweep's loads */
+    auto block = [&](int b) { return lk_block_checked<MODEL, G, KM>(ln, a, b, L, Tp, xbad); };
     double w[KM];
     int slot = 0;
 
@@ -273,96 +261,56 @@ __global__ void __launch_bounds__(kBlock) draw_stats_large_kernel(const DevArgs 
 
 /* ---- host side ---- */
 
-static int dsl_G(int K) { return K <= 16 ? 16 : 32; }
-
 /* LDS bytes of one group: two exchange slots and the xi rows (32-bit);
  * hmm-multinom: the phi table (fp64) and its count table (32-bit) too, i.e.
  * G * (16 + 12 L + 4 K). */
 static size_t dsl_group_lds(int model, int K, int L)
 {
-    const size_t G = (size_t)dsl_G(K), tabs = model == HHMM_MODEL_HMM_GAUSS ? 0 : (size_t)L;
+    const size_t G = (size_t)lk_G(K), tabs = model == HHMM_MODEL_HMM_GAUSS ? 0 : (size_t)L;
     return (2 + tabs) * G * sizeof(double) + (tabs + (size_t)K) * G * sizeof(uint32_t);
 }
 
-/* Threads per workgroup and its LDS: group_threads' rule (hhmm_stats.h), the
- * groups' LDS beside the workgroup's det-exp table for hmm. */
-static int dsl_threads(int model, int K, int L, size_t *lds)
+/* lk_geometry (hhmm_stats.h) of the groups' LDS beside the workgroup's det-exp table for hmm */
+static bool dsl_geometry(int model, int K, int L, int64_t P, LkGeom *g)
 {
     const size_t tab = model == HHMM_MODEL_HMM_GAUSS ? kDslTabBytes : 0;
-    return group_threads(dsl_group_lds(model, K, L), dsl_G(K), lds, tab);
+    return lk_geometry(dsl_group_lds(model, K, L), tab, lk_G(K), P, g);
 }
-
-size_t draw_stats_large_workspace_bytes(int K, int Tmax, int64_t P)
-{
-    return (size_t)(((int64_t)Tmax + kLChunk - 1) / kLChunk) * (size_t)K * (size_t)P * sizeof(double);
-}
-
-static bool dsl_model(int m) { return m == HHMM_MODEL_HMM_GAUSS || m == HHMM_MODEL_HMM_MULTINOM; }
 
 hhmm_status check_draw_stats_large(const hhmm_request *r, const hhmm_estep_result *o)
 {
-    const hhmm_status s = stats_check_head("large-K draw statistics", r, dsl_model,
-                                           "hmm and hmm-multinom only; hmm-multinom-semisup and hhmm-tayal2009 are "
-                                           "K <= 8 programs (hhmm_draw_stats)",
-                                           kMaxK + 1, kMaxKLarge, "hhmm_draw_stats / hhmm_draw_stats_gauss");
+    const LkScope &sc = kDrawStatsLargeScope;
+    const hhmm_status s = stats_check_head(sc.name, r, lk_stats_model, sc.others, sc.k_lo, sc.k_hi, sc.below);
     if (s != HHMM_OK)
         return s;
-    if (r->model == HHMM_MODEL_HMM_MULTINOM && r->data.L >= 1) {
-        size_t lds;
-        if (dsl_threads(r->model, r->data.K, r->data.L, &lds) < 1) {
-            const int G = dsl_G(r->data.K);
-            set_error("large-K draw statistics: L = %d: %d * (16 + 12 * L + 4 * K) = %zu > %zu bytes: the emission "
-                      "table, its count table and the xi rows of one %d-lane group do not fit in LDS",
-                      r->data.L, G, dsl_group_lds(r->model, r->data.K, r->data.L), kLdsLimit, G);
-            return HHMM_ERR_UNSUPPORTED;
-        }
+    const int K = r->data.K, L = r->data.L, G = lk_G(K);
+    LkGeom g;
+    if (r->model == HHMM_MODEL_HMM_MULTINOM && L >= 1 && !dsl_geometry(r->model, K, L, 1, &g)) {
+        set_error("%s: L = %d: %d * (16 + 12 * L + 4 * K) = %zu > %zu bytes: the emission table, its count table and "
+                  "the xi rows of one %d-lane group do not fit in LDS",
+                  sc.name, L, G, dsl_group_lds(r->model, K, L), kLdsLimit, G);
+        return HHMM_ERR_UNSUPPORTED;
     }
-    return stats_check_tail("large-K draw statistics", r, o, true);
-}
-
-template <int MODEL>
-static void launch_dsl_m(const DevArgs &a, const DrawStatsLargeOut &o, dim3 grid, dim3 block, size_t lds,
-                         hipStream_t st)
-{
-    /* the instances of lk_ffbs_kernel (run_large, hhmm_m_large.hip) */
-    if (a.K <= 16)
-        hipLaunchKernelGGL((draw_stats_large_kernel<MODEL, 16, 16>), grid, block, lds, st, a, o);
-    else if (a.K <= 24)
-        hipLaunchKernelGGL((draw_stats_large_kernel<MODEL, 32, 24>), grid, block, lds, st, a, o);
-    else
-        hipLaunchKernelGGL((draw_stats_large_kernel<MODEL, 32, 32>), grid, block, lds, st, a, o);
+    return stats_check_tail(sc.name, r, o, sc.reads_u);
 }
 
 hhmm_status launch_draw_stats_large(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                                     hipStream_t st)
 {
-    DevArgs a = stats_dev_args(r, P, ws);
-    a.x = r->data.x_int;
-    a.xr = r->data.x_real;
-    a.phi_k = r->draws.phi_k;
-    a.mu_k = r->draws.mu_k;
-    a.sigma_k = r->draws.sigma_k;
-    a.ffbs_u = r->ffbs_u;
-    if (a.model == HHMM_MODEL_HMM_GAUSS)
-        a.L = 0; /* no tables: lk_setup lays the LDS out by L */
-    if (a.K <= kMaxK || a.K > kMaxKLarge) {
-        set_error("large-K draw statistics: K = %d outside %d..%d", a.K, kMaxK + 1, kMaxKLarge);
+    const LkScope &sc = kDrawStatsLargeScope;
+    DevArgs a;
+    const hhmm_status s = lk_stats_dev_args(sc, r, P, ws, &a);
+    if (s != HHMM_OK)
+        return s;
+    LkGeom g;
+    if (!dsl_geometry(a.model, a.K, a.L, P, &g)) {
+        set_error("%s: the tables of L = %d do not fit in LDS", sc.name, a.L);
         return HHMM_ERR_UNSUPPORTED;
     }
-    DrawStatsLargeOut o{res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->w_k, res->s1_k, res->s2_k,
-                        res->pair_status};
-    size_t lds = 0;
-    const int threads = dsl_threads(a.model, a.K, a.L, &lds);
-    if (threads < 1) {
-        set_error("large-K draw statistics: the tables of L = %d do not fit in LDS", a.L);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    const int gpb = threads / dsl_G(a.K);
-    const dim3 grid((unsigned)((P + gpb - 1) / gpb)), block(threads);
-    if (a.model == HHMM_MODEL_HMM_GAUSS)
-        launch_dsl_m<HHMM_MODEL_HMM_GAUSS>(a, o, grid, block, lds, st);
-    else
-        launch_dsl_m<HHMM_MODEL_HMM_MULTINOM>(a, o, grid, block, lds, st);
+    const LkStatsOut o = lk_stats_out(res);
+    dispatch_lk_model(a.model, a.K, [&](auto M, auto G, auto KM) { /* the instances of lk_ffbs_kernel (run_large) */
+        hipLaunchKernelGGL((draw_stats_large_kernel<M, G, KM>), g.grid, g.block, g.lds, st, a, o);
+    });
     return launch_status("draw_stats_large_kernel");
 }
 

@@ -44,11 +44,6 @@
 
 namespace hhmm {
 
-struct EstepLargeOut {
-    double *loglik, *n1, *xi, *c, *w, *s1, *s2;
-    int32_t *status;
-};
-
 /* Where row i of xi lives, per instance: registers where the kernel keeps two
  * waves per SIMD with them (KM = 16) or has one in either form (KM = 32, and
  * hmm at KM = 24); the per-pair LDS block for hmm-multinom at KM = 24, where KM
@@ -57,7 +52,7 @@ struct EstepLargeOut {
 constexpr bool estep_large_xi_lds(bool gauss, int KM) { return !gauss && KM == 24; }
 
 template <int MODEL, int G, int KM>
-__global__ void __launch_bounds__(kBlock) estep_large_kernel(const DevArgs a, const EstepLargeOut o)
+__global__ void __launch_bounds__(kBlock) estep_large_kernel(const DevArgs a, const LkStatsOut o)
 {
     HIP_DYNAMIC_SHARED(double, lds)
     constexpr bool GAUSS = LkTraits<MODEL>::kGauss;
@@ -87,15 +82,8 @@ __global__ void __launch_bounds__(kBlock) estep_large_kernel(const DevArgs a, co
     };
     auto xchg = [&](int sl, double v, double (&wv)[KM]) { grp_exchange<G, KM>(ln.xch, sl, ln.j, v, wv); };
     auto ckpt = [&](int c) -> double & { return a.ckpt[q + a.P * ((int64_t)c * K + (ln.on ? ln.j : 0))]; };
-    /* the data check rides on the forward sweep's loads: lane j of the group
-     * tests the symbol of step b * G + j (steps of the series only) */
-    bool xbad = false;
-    auto block = [&](int b) {
-        const LkObs<MODEL, G> ob = lk_block<MODEL, G, KM>(ln, a, b);
-        if constexpr (!GAUSS)
-            xbad |= (b * G + ln.j < Tp) & ((ob.x < 1) | (ob.x > L));
-        return ob;
-    };
+    bool xbad = false; /* the data check rides on the forward sweep's loads */
+    auto block = [&](int b) { return lk_block_checked<MODEL, G, KM>(ln, a, b, L, Tp, xbad); };
     double w[KM];
     int slot = 0;
 
@@ -270,7 +258,7 @@ __global__ void __launch_bounds__(kBlock) estep_large_kernel(const DevArgs a, co
     }
     /* any lane of the group saw a symbol outside 1..L (every lane of the wave takes part) */
     const unsigned long long hit = __ballot(xbad);
-    const unsigned long long mine = (G == 64 ? ~0ull : ((1ull << G) - 1)) << ((threadIdx.x & 63) & ~(G - 1));
+    const unsigned long long mine = ((1ull << G) - 1) << ((threadIdx.x & 63) & ~(G - 1));
     if (ln.j == 0) {
         o.loglik[p] = ll;
         if (o.status) {
@@ -284,93 +272,55 @@ __global__ void __launch_bounds__(kBlock) estep_large_kernel(const DevArgs a, co
 
 /* ---- host side ---- */
 
-static int estep_large_G(int K) { return K <= 16 ? 16 : 32; }
-static int estep_large_KM(int K) { return K <= 16 ? 16 : (K <= 24 ? 24 : 32); }
-
 /* LDS bytes of one group: two exchange slots, the phi table and the count
  * table of hmm-multinom, the xi rows where the instance keeps them there. */
 static size_t estep_large_group_lds(int model, int K, int L)
 {
-    const size_t G = (size_t)estep_large_G(K);
+    const size_t G = (size_t)lk_G(K);
     const size_t tabs = model == HHMM_MODEL_HMM_GAUSS ? 0 : 2 * (size_t)L;
-    const bool xl = estep_large_xi_lds(model == HHMM_MODEL_HMM_GAUSS, estep_large_KM(K));
+    const bool xl = estep_large_xi_lds(model == HHMM_MODEL_HMM_GAUSS, lk_KM(K));
     return ((2 + tabs) * G + (xl ? (size_t)K * G : 0)) * sizeof(double);
 }
 
-/* Threads per workgroup and its LDS: group_threads' rule (hhmm_stats.h). */
-static int estep_large_threads(int model, int K, int L, size_t *lds)
+size_t lk_ckpt_workspace_bytes(const hhmm_request *r, int64_t P)
 {
-    return group_threads(estep_large_group_lds(model, K, L), estep_large_G(K), lds);
+    return (size_t)(((int64_t)r->data.T_max + kLChunk - 1) / kLChunk) * (size_t)r->data.K * (size_t)P * sizeof(double);
 }
-
-size_t estep_large_workspace_bytes(int K, int Tmax, int64_t P)
-{
-    return (size_t)(((int64_t)Tmax + kLChunk - 1) / kLChunk) * (size_t)K * (size_t)P * sizeof(double);
-}
-
-static bool estep_large_model(int m) { return m == HHMM_MODEL_HMM_GAUSS || m == HHMM_MODEL_HMM_MULTINOM; }
 
 hhmm_status check_estep_large(const hhmm_request *r, const hhmm_estep_result *o)
 {
-    const hhmm_status s = stats_check_head("large-K E-step", r, estep_large_model,
-                                           "hmm and hmm-multinom only; the other programs have no state-parallel "
-                                           "E-step",
-                                           kMaxK + 1, kMaxKLarge);
+    const LkScope &sc = kEstepLargeScope;
+    const hhmm_status s = stats_check_head(sc.name, r, lk_stats_model, sc.others, sc.k_lo, sc.k_hi, sc.below);
     if (s != HHMM_OK)
         return s;
-    if (r->model == HHMM_MODEL_HMM_MULTINOM && r->data.L >= 1) {
-        size_t lds;
-        if (estep_large_threads(r->model, r->data.K, r->data.L, &lds) < 1) {
-            set_error("large-K E-step: L = %d: the emission table and its count table of one %d-lane group do not "
-                      "fit in LDS",
-                      r->data.L, estep_large_G(r->data.K));
-            return HHMM_ERR_UNSUPPORTED;
-        }
+    const int K = r->data.K, L = r->data.L;
+    LkGeom g;
+    if (r->model == HHMM_MODEL_HMM_MULTINOM && L >= 1 &&
+        !lk_geometry(estep_large_group_lds(r->model, K, L), 0, lk_G(K), 1, &g)) {
+        set_error("%s: L = %d: the emission table and its count table of one %d-lane group do not fit in LDS", sc.name,
+                  L, lk_G(K));
+        return HHMM_ERR_UNSUPPORTED;
     }
-    return stats_check_tail("large-K E-step", r, o, false);
-}
-
-template <int MODEL>
-static void launch_estep_large_m(const DevArgs &a, const EstepLargeOut &o, dim3 grid, dim3 block, size_t lds,
-                                 hipStream_t st)
-{
-    /* the instances of run_large (hhmm_m_large.hip) */
-    if (a.K <= 16)
-        hipLaunchKernelGGL((estep_large_kernel<MODEL, 16, 16>), grid, block, lds, st, a, o);
-    else if (a.K <= 24)
-        hipLaunchKernelGGL((estep_large_kernel<MODEL, 32, 24>), grid, block, lds, st, a, o);
-    else
-        hipLaunchKernelGGL((estep_large_kernel<MODEL, 32, 32>), grid, block, lds, st, a, o);
+    return stats_check_tail(sc.name, r, o, sc.reads_u);
 }
 
 hhmm_status launch_estep_large(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                                hipStream_t st)
 {
-    DevArgs a = stats_dev_args(r, P, ws);
-    a.x = r->data.x_int;
-    a.xr = r->data.x_real;
-    a.phi_k = r->draws.phi_k;
-    a.mu_k = r->draws.mu_k;
-    a.sigma_k = r->draws.sigma_k;
-    if (a.model == HHMM_MODEL_HMM_GAUSS)
-        a.L = 0; /* no tables: lk_setup lays the LDS out by L */
-    if (a.K <= kMaxK || a.K > kMaxKLarge) {
-        set_error("large-K E-step: K = %d outside %d..%d", a.K, kMaxK + 1, kMaxKLarge);
+    const LkScope &sc = kEstepLargeScope;
+    DevArgs a;
+    const hhmm_status s = lk_stats_dev_args(sc, r, P, ws, &a);
+    if (s != HHMM_OK)
+        return s;
+    LkGeom g;
+    if (!lk_geometry(estep_large_group_lds(a.model, a.K, a.L), 0, lk_G(a.K), P, &g)) {
+        set_error("%s: the tables of L = %d do not fit in LDS", sc.name, a.L);
         return HHMM_ERR_UNSUPPORTED;
     }
-    EstepLargeOut o{res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->w_k, res->s1_k, res->s2_k, res->pair_status};
-    size_t lds = 0;
-    const int threads = estep_large_threads(a.model, a.K, a.L, &lds);
-    if (threads < 1) {
-        set_error("large-K E-step: the tables of L = %d do not fit in LDS", a.L);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    const int gpb = threads / estep_large_G(a.K);
-    const dim3 grid((unsigned)((P + gpb - 1) / gpb)), block(threads);
-    if (a.model == HHMM_MODEL_HMM_GAUSS)
-        launch_estep_large_m<HHMM_MODEL_HMM_GAUSS>(a, o, grid, block, lds, st);
-    else
-        launch_estep_large_m<HHMM_MODEL_HMM_MULTINOM>(a, o, grid, block, lds, st);
+    const LkStatsOut o = lk_stats_out(res);
+    dispatch_lk_model(a.model, a.K, [&](auto M, auto G, auto KM) { /* the instances of run_large (hhmm_m_large.hip) */
+        hipLaunchKernelGGL((estep_large_kernel<M, G, KM>), g.grid, g.block, g.lds, st, a, o);
+    });
     return launch_status("estep_large_kernel");
 }
 

@@ -178,6 +178,17 @@ hhmm_status selftest_cr_math(const double *in, double *out, int64_t n, int which
 
 void set_error(const char *fmt, ...);
 
+/* hhmm_api.cpp's, for the statistics entries (hhmm_stats_api.cpp): the device
+ * pool (pool_get: NULL when the device has no memory left; pool_put(NULL) is
+ * fine), the request checks of hhmm_run (o == NULL: the request side only;
+ * host: the data-block bounds too), "is there a device", and the status of a
+ * failed HIP call with its message. */
+void *pool_get(int dev, size_t bytes);
+void pool_put(void *ptr);
+hhmm_status validate_impl(const hhmm_request *r, const hhmm_result *o, bool host);
+hhmm_status check_device();
+hhmm_status hip_fail(hipError_t e, const char *what);
+
 /* Waves per workgroup, at most kBlock / 64, whose tables of per_wave bytes
  * each fit in LDS together (0: not even one), and the workgroup's LDS. */
 inline int waves_that_fit(size_t per_wave, size_t *lds, int waves = kBlock / 64)

@@ -37,6 +37,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "hhmm_device.h"
 
 namespace hhmm {
@@ -73,6 +75,29 @@ template <int MODEL>
 struct LkTraits {
     static constexpr bool kGauss = (MODEL == HHMM_MODEL_HMM_GAUSS);
 };
+
+/* The instance of K: the group width G and the bound KM of the compile-time
+ * state loops (32-lane groups carry 24 or 32 states). */
+constexpr int lk_G(int K) { return K <= 16 ? 16 : 32; }
+constexpr int lk_KM(int K) { return K <= 16 ? 16 : (K <= 24 ? 24 : 32); }
+
+/* f(G, KM) as std::integral_constants for kMaxK < K <= kMaxKLarge (the caller
+ * has checked the range), and what it returns; after dispatch_k (hhmm_stats.h). */
+template <int V>
+using LkC = std::integral_constant<int, V>;
+template <class F>
+auto dispatch_lk(int K, F &&f)
+{
+    return K <= 16 ? f(LkC<16>{}, LkC<16>{}) : K <= 24 ? f(LkC<32>{}, LkC<24>{}) : f(LkC<32>{}, LkC<32>{});
+}
+/* The same with the model in front: f(MODEL, G, KM) for hmm, else hmm-multinom. */
+template <class F>
+auto dispatch_lk_model(int model, int K, F &&f)
+{
+    if (model == HHMM_MODEL_HMM_GAUSS)
+        return dispatch_lk(K, [&](auto G, auto KM) { return f(LkC<HHMM_MODEL_HMM_GAUSS>{}, G, KM); });
+    return dispatch_lk(K, [&](auto G, auto KM) { return f(LkC<HHMM_MODEL_HMM_MULTINOM>{}, G, KM); });
+}
 
 /* Group reductions over the 32 lanes of a pair (one aligned half of the
  * wave): a butterfly of DPP moves inside each 16-lane row (quad xor 1, quad
@@ -264,6 +289,19 @@ __device__ __forceinline__ LkObs<MODEL, G> lk_block(const LkLane<MODEL, G, KM> &
     else
         o.x = a.x[ln.n + a.N * (int64_t)tc];
     return o;
+}
+
+/* lk_block with the data check of the statistics kernels riding on its load:
+ * lane j of the group tests the symbol of step b * G + j (steps of the series
+ * only) against 1..L */
+template <int MODEL, int G, int KM>
+__device__ __forceinline__ LkObs<MODEL, G> lk_block_checked(const LkLane<MODEL, G, KM> &ln, const DevArgs &a, int b,
+                                                            int L, int Tp, bool &xbad)
+{
+    const LkObs<MODEL, G> ob = lk_block<MODEL, G, KM>(ln, a, b);
+    if constexpr (!LkTraits<MODEL>::kGauss)
+        xbad |= (b * G + ln.j < Tp) & ((ob.x < 1) | (ob.x > L));
+    return ob;
 }
 
 /* step u of the block: lane u of the group; u is wave-uniform, so two scalar

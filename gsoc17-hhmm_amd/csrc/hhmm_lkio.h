@@ -479,9 +479,7 @@ static hhmm_status launch_lkio(const DevArgs &a, hipStream_t st)
         set_error("large-K IOHMM: M = %d (at most %d), L = %d (at most %d)", a.M, kLkioMmax, a.L, kIoLmax);
         return HHMM_ERR_UNSUPPORTED;
     }
-    return a.K <= 16 ? launch_lkio_g<FAM, 16, 16>(a, st)
-           : a.K <= 24 ? launch_lkio_g<FAM, 32, 24>(a, st)
-                       : launch_lkio_g<FAM, 32, 32>(a, st);
+    return dispatch_lk(a.K, [&](auto G, auto KM) { return launch_lkio_g<FAM, G, KM>(a, st); });
 }
 
 /* ---- fitted-output draws at large K (fitted_kernel's arithmetic) ----
@@ -609,9 +607,7 @@ static hhmm_status launch_lkfit(const DevArgs &a, hipStream_t st)
         set_error("large-K fitted draws: M = %d (at most %d), L = %d (at most %d)", a.M, kLkioMmax, a.L, kIoLmax);
         return HHMM_ERR_UNSUPPORTED;
     }
-    return a.K <= 16 ? launch_lkfit_g<FAM, 16, 16>(a, st)
-           : a.K <= 24 ? launch_lkfit_g<FAM, 32, 24>(a, st)
-                       : launch_lkfit_g<FAM, 32, 32>(a, st);
+    return dispatch_lk(a.K, [&](auto G, auto KM) { return launch_lkfit_g<FAM, G, KM>(a, st); });
 }
 
 } // namespace hhmm

@@ -7,14 +7,7 @@ namespace hhmm {
 
 hhmm_status run_large(const DevArgs &a, hipStream_t st)
 {
-    /* 32-lane groups carry 24 or 32 states in their compile-time loops */
-    if (a.model == HHMM_MODEL_HMM_GAUSS)
-        return a.K <= 16 ? run_large_model<HHMM_MODEL_HMM_GAUSS, 16, 16>(a, st)
-               : a.K <= 24 ? run_large_model<HHMM_MODEL_HMM_GAUSS, 32, 24>(a, st)
-                           : run_large_model<HHMM_MODEL_HMM_GAUSS, 32, 32>(a, st);
-    return a.K <= 16 ? run_large_model<HHMM_MODEL_HMM_MULTINOM, 16, 16>(a, st)
-           : a.K <= 24 ? run_large_model<HHMM_MODEL_HMM_MULTINOM, 32, 24>(a, st)
-                       : run_large_model<HHMM_MODEL_HMM_MULTINOM, 32, 32>(a, st);
+    return dispatch_lk_model(a.model, a.K, [&](auto M, auto G, auto KM) { return run_large_model<M, G, KM>(a, st); });
 }
 
 } // namespace hhmm

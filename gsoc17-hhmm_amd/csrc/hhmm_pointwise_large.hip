@@ -76,15 +76,8 @@ __global__ void __launch_bounds__(kBlock) pointwise_large_kernel(const DevArgs a
     LkLane<MODEL, G, KM> ln;
     lk_setup<MODEL, G, KM>(ln, a, lds, false, q);
     const int L = GAUSS ? 0 : ln.L, Tp = ln.Tp;
-    /* the data check rides on the forward sweep's loads: lane j of the group
-     * tests the symbol of step b * G + j (steps of the series only) */
-    bool xbad = false;
-    auto block = [&](int b) {
-        const LkObs<MODEL, G> ob = lk_block<MODEL, G, KM>(ln, a, b);
-        if constexpr (!GAUSS)
-            xbad |= (b * G + ln.j < Tp) & ((ob.x < 1) | (ob.x > L));
-        return ob;
-    };
+    bool xbad = false; /* the data check rides on the forward sweep's loads */
+    auto block = [&](int b) { return lk_block_checked<MODEL, G, KM>(ln, a, b, L, Tp, xbad); };
     double w[KM];
     int slot = 0;
 
@@ -254,18 +247,11 @@ __global__ void __launch_bounds__(kBlock) pointwise_large_reduce_kernel(const De
 
 /* ---- host side ---- */
 
-static int pwl_G(int K) { return K <= 16 ? 16 : 32; }
-
 /* LDS bytes of one group: two exchange slots and the phi table of hmm-multinom. */
 static size_t pwl_group_lds(int model, int K, int L)
 {
     const size_t tab = model == HHMM_MODEL_HMM_GAUSS ? 0 : (size_t)L;
-    return (2 + tab) * (size_t)pwl_G(K) * sizeof(double);
-}
-
-static int pwl_threads(int model, int K, int L, size_t *lds)
-{
-    return group_threads(pwl_group_lds(model, K, L), pwl_G(K), lds);
+    return (2 + tab) * (size_t)lk_G(K) * sizeof(double);
 }
 
 size_t pointwise_large_workspace_bytes(const hhmm_request *r, int64_t P)
@@ -273,48 +259,30 @@ size_t pointwise_large_workspace_bytes(const hhmm_request *r, int64_t P)
     return (size_t)P * (size_t)r->data.T_max * sizeof(double);
 }
 
-static bool pwl_model(int m) { return m == HHMM_MODEL_HMM_GAUSS || m == HHMM_MODEL_HMM_MULTINOM; }
-
 hhmm_status check_pointwise_large(const hhmm_request *r, const hhmm_pointwise_result *o)
 {
-    const hhmm_status s = stats_check_head("large-K pointwise", r, pwl_model,
-                                           "hmm and hmm-multinom only; the coded step weights of the semisup, Tayal "
-                                           "and IOHMM programs are masked or factorised, not a predictive density",
-                                           kMaxK + 1, kMaxKLarge, "hhmm_pointwise");
+    const LkScope &sc = kPointwiseLargeScope;
+    const hhmm_status s = stats_check_head(sc.name, r, lk_stats_model, sc.others, sc.k_lo, sc.k_hi, sc.below);
     if (s != HHMM_OK)
         return s;
-    if (r->model == HHMM_MODEL_HMM_MULTINOM && r->data.L >= 1) {
-        size_t lds;
-        if (pwl_threads(r->model, r->data.K, r->data.L, &lds) < 1) {
-            const int G = pwl_G(r->data.K);
-            set_error("large-K pointwise: L = %d: (2 + L) * %d * 8 = %zu > %zu bytes: the emission table of one "
-                      "%d-lane group does not fit in LDS",
-                      r->data.L, G, pwl_group_lds(r->model, r->data.K, r->data.L), kLdsLimit, G);
-            return HHMM_ERR_UNSUPPORTED;
-        }
+    const int K = r->data.K, L = r->data.L, G = lk_G(K);
+    LkGeom g;
+    if (r->model == HHMM_MODEL_HMM_MULTINOM && L >= 1 && !lk_geometry(pwl_group_lds(r->model, K, L), 0, G, 1, &g)) {
+        set_error("%s: L = %d: (2 + L) * %d * 8 = %zu > %zu bytes: the emission table of one %d-lane group does not "
+                  "fit in LDS",
+                  sc.name, L, G, pwl_group_lds(r->model, K, L), kLdsLimit, G);
+        return HHMM_ERR_UNSUPPORTED;
     }
     if (!o) {
-        set_error("large-K pointwise: result must be non-NULL");
+        set_error("%s: result must be non-NULL", sc.name);
         return HHMM_ERR_INVALID_ARGUMENT;
     }
     const char *missing = !o->loglik ? "loglik" : !o->lpd_t ? "lpd_t" : !o->mean_t ? "mean_t" : !o->var_t ? "var_t" : nullptr;
     if (missing) {
-        set_error("large-K pointwise: %s must be non-NULL (loglik, lpd_t, mean_t and var_t are required)", missing);
+        set_error("%s: %s must be non-NULL (loglik, lpd_t, mean_t and var_t are required)", sc.name, missing);
         return HHMM_ERR_INVALID_ARGUMENT;
     }
     return HHMM_OK;
-}
-
-template <int MODEL>
-static void launch_pwl_m(const DevArgs &a, const PwlOut &o, dim3 grid, dim3 block, size_t lds, hipStream_t st)
-{
-    /* the instances of launch_estep_large_m */
-    if (a.K <= 16)
-        hipLaunchKernelGGL((pointwise_large_kernel<MODEL, 16, 16>), grid, block, lds, st, a, o);
-    else if (a.K <= 24)
-        hipLaunchKernelGGL((pointwise_large_kernel<MODEL, 32, 24>), grid, block, lds, st, a, o);
-    else
-        hipLaunchKernelGGL((pointwise_large_kernel<MODEL, 32, 32>), grid, block, lds, st, a, o);
 }
 
 template <int W>
@@ -328,34 +296,22 @@ static void launch_pwl_reduce(const DevArgs &a, const PwlRed &o, hipStream_t st)
 hhmm_status launch_pointwise_large(const hhmm_request *r, const hhmm_pointwise_result *res, int64_t P, void *ws,
                                    hipStream_t st)
 {
-    DevArgs a = stats_dev_args(r, P, nullptr);
-    a.x = r->data.x_int;
-    a.xr = r->data.x_real;
-    a.phi_k = r->draws.phi_k;
-    a.mu_k = r->draws.mu_k;
-    a.sigma_k = r->draws.sigma_k;
-    if (a.model == HHMM_MODEL_HMM_GAUSS)
-        a.L = 0; /* no tables: lk_setup lays the LDS out by L */
-    if (a.K <= kMaxK || a.K > kMaxKLarge) {
-        set_error("large-K pointwise: K = %d outside %d..%d", a.K, kMaxK + 1, kMaxKLarge);
-        return HHMM_ERR_UNSUPPORTED;
-    }
-    size_t lds = 0;
-    const int threads = pwl_threads(a.model, a.K, a.L, &lds);
-    if (threads < 1) {
-        set_error("large-K pointwise: the table of L = %d does not fit in LDS", a.L);
+    const LkScope &sc = kPointwiseLargeScope;
+    DevArgs a;
+    hhmm_status s = lk_stats_dev_args(sc, r, P, nullptr, &a);
+    if (s != HHMM_OK)
+        return s;
+    LkGeom g;
+    if (!lk_geometry(pwl_group_lds(a.model, a.K, a.L), 0, lk_G(a.K), P, &g)) {
+        set_error("%s: the table of L = %d does not fit in LDS", sc.name, a.L);
         return HHMM_ERR_UNSUPPORTED;
     }
     double *const lp = res->lp_t ? res->lp_t : (double *)ws; /* the workspace is not touched when lp_t is given */
     const PwlOut o{res->loglik, lp, res->pair_status};
-    const int gpb = threads / pwl_G(a.K);
-    const dim3 grid((unsigned)((P + gpb - 1) / gpb)), block(threads);
-    if (a.model == HHMM_MODEL_HMM_GAUSS)
-        launch_pwl_m<HHMM_MODEL_HMM_GAUSS>(a, o, grid, block, lds, st);
-    else
-        launch_pwl_m<HHMM_MODEL_HMM_MULTINOM>(a, o, grid, block, lds, st);
-    const hhmm_status s = launch_status("pointwise_large_kernel");
-    if (s != HHMM_OK)
+    dispatch_lk_model(a.model, a.K, [&](auto M, auto G, auto KM) { /* the instances of estep_large_kernel */
+        hipLaunchKernelGGL((pointwise_large_kernel<M, G, KM>), g.grid, g.block, g.lds, st, a, o);
+    });
+    if ((s = launch_status("pointwise_large_kernel")) != HHMM_OK)
         return s;
     const PwlRed q{lp, res->lpd_t, res->mean_t, res->var_t, P / a.N};
     if (q.D <= 16)

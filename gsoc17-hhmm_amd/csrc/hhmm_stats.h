@@ -27,8 +27,8 @@
 
 namespace hhmm {
 
-/* Each of the eleven entries gives the host path of hhmm_api.cpp (StatsEntry,
- * stats_*) a check_* and a launch_*; what those share follows them.
+/* Each of the eleven entries gives the host path of hhmm_stats_api.cpp
+ * (StatsEntry, stats_*) a check_* and a launch_*; what those share follows them.
  *
  * Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
  * checkpoint workspace and the launch on `st` (device pointers). */
@@ -37,9 +37,8 @@ size_t estep_workspace_bytes(int K, int Tmax, int64_t P);
 hhmm_status launch_estep(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws, hipStream_t st);
 
 /* Batched E-step at kMaxK < K <= kMaxKLarge (hhmm_estep_large.hip): the same
- * three; the workspace is the forward checkpoints every kLChunk steps. */
+ * pair; the workspace is lk_ckpt_workspace_bytes. */
 hhmm_status check_estep_large(const hhmm_request *r, const hhmm_estep_result *o);
-size_t estep_large_workspace_bytes(int K, int Tmax, int64_t P);
 hhmm_status launch_estep_large(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                                hipStream_t st);
 
@@ -56,10 +55,8 @@ hhmm_status launch_draw_stats_gauss(const hhmm_request *r, const hhmm_estep_resu
                                     hipStream_t st);
 
 /* Draw statistics at kMaxK < K <= kMaxKLarge (hhmm_draw_stats_large.hip), hmm
- * and hmm-multinom: the same pair; the workspace is the forward checkpoints
- * every kLChunk steps (the large-K E-step's size). */
+ * and hmm-multinom: the same pair; the workspace is lk_ckpt_workspace_bytes. */
 hhmm_status check_draw_stats_large(const hhmm_request *r, const hhmm_estep_result *o);
-size_t draw_stats_large_workspace_bytes(int K, int Tmax, int64_t P);
 hhmm_status launch_draw_stats_large(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                                     hipStream_t st);
 
@@ -219,6 +216,86 @@ inline int group_threads(size_t per, int G, size_t *lds, size_t fixed = 0)
     }
     *lds = fixed + (size_t)(threads / G) * per;
     return *lds > kLdsLimit ? 0 : threads;
+}
+
+/* ---- the state-parallel entries: hmm and hmm-multinom at kMaxK < K <=
+ * kMaxKLarge, a group of lk_G(K) lanes per pair (hhmm_large.h) ---- */
+
+/* What an entry says of itself, once: check_*, launch_* and its StatsEntry row read it. */
+struct LkScope {
+    const char *name;   /* in messages */
+    bool reads_u;       /* ffbs_u is an input */
+    const char *others; /* where the other models go (stats_check_head's `scope`) */
+    const char *below;  /* the entry that takes K <= kMaxK */
+    int k_lo = kMaxK + 1, k_hi = kMaxKLarge;
+};
+inline constexpr LkScope kEstepLargeScope = {
+    "large-K E-step", false, "hmm and hmm-multinom only; the other programs have no state-parallel E-step",
+    "hhmm_estep"};
+inline constexpr LkScope kDrawStatsLargeScope = {
+    "large-K draw statistics", true,
+    "hmm and hmm-multinom only; hmm-multinom-semisup and hhmm-tayal2009 are K <= 8 programs (hhmm_draw_stats)",
+    "hhmm_draw_stats / hhmm_draw_stats_gauss"};
+inline constexpr LkScope kPointwiseLargeScope = {
+    "large-K pointwise", false,
+    "hmm and hmm-multinom only; the coded step weights of the semisup, Tayal and IOHMM programs are masked or "
+    "factorised, not a predictive density",
+    "hhmm_pointwise"};
+
+inline bool lk_stats_model(int m) { return m == HHMM_MODEL_HMM_GAUSS || m == HHMM_MODEL_HMM_MULTINOM; }
+
+/* The forward checkpoints every kLChunk steps, [chunks][K][P] doubles: the
+ * workspace of the E-step and of the draw statistics (hhmm_estep_large.hip). */
+size_t lk_ckpt_workspace_bytes(const hhmm_request *r, int64_t P);
+
+/* The DevArgs of a launch: stats_dev_args, the data and draw arrays of the two
+ * models, the uniforms where the entry reads them; L = 0 for the Gaussian hmm
+ * (no tables: lk_setup lays the LDS out by L). */
+inline hhmm_status lk_stats_dev_args(const LkScope &sc, const hhmm_request *r, int64_t P, void *ws, DevArgs *a)
+{
+    *a = stats_dev_args(r, P, ws);
+    a->x = r->data.x_int;
+    a->xr = r->data.x_real;
+    a->phi_k = r->draws.phi_k;
+    a->mu_k = r->draws.mu_k;
+    a->sigma_k = r->draws.sigma_k;
+    if (sc.reads_u)
+        a->ffbs_u = r->ffbs_u;
+    if (a->model == HHMM_MODEL_HMM_GAUSS)
+        a->L = 0;
+    if (a->K < sc.k_lo || a->K > sc.k_hi) {
+        set_error("%s: K = %d outside %d..%d", sc.name, a->K, sc.k_lo, sc.k_hi);
+        return HHMM_ERR_UNSUPPORTED;
+    }
+    return HHMM_OK;
+}
+
+/* The outputs of an hhmm_estep_result as a kernel argument (the E-step and the draw statistics). */
+struct LkStatsOut {
+    double *loglik, *n1, *xi, *c, *w, *s1, *s2;
+    int32_t *status;
+};
+inline LkStatsOut lk_stats_out(const hhmm_estep_result *res)
+{
+    return {res->loglik, res->n_1k, res->xi_ij, res->c_kl, res->w_k, res->s1_k, res->s2_k, res->pair_status};
+}
+
+/* Workgroup, its LDS and the grid over P pairs by group_threads' rule, from the
+ * entry's `per` LDS bytes per G-lane group and `fixed` per workgroup.  false:
+ * one group does not fit; the entry words the refusal. */
+struct LkGeom {
+    dim3 grid, block;
+    size_t lds;
+};
+inline bool lk_geometry(size_t per, size_t fixed, int G, int64_t P, LkGeom *g)
+{
+    const int threads = group_threads(per, G, &g->lds, fixed);
+    if (threads < 1)
+        return false;
+    const int gpb = threads / G;
+    g->grid = dim3((unsigned)((P + gpb - 1) / gpb));
+    g->block = dim3(threads);
+    return true;
 }
 
 /* waves_that_fit and launch_status: hhmm_internal.h (the HMM family's launchers use them too).
