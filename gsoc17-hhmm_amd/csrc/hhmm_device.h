@@ -7,6 +7,8 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
+#include <type_traits>
+
 #include "hhmm_internal.h"
 
 #ifndef HHMM_MATH_FN
@@ -209,6 +211,87 @@ __device__ __forceinline__ T get_tmp(const T *row, uint32_t byte_off)
     return at(row, byte_off);
 }
 
+/* A 64-bit value the whole wave shares, told to hipcc as such (readfirstlane
+ * on both halves): what is derived from it stays on the scalar unit. */
+__device__ __forceinline__ int64_t wave_uniform(int64_t v)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+/* A wave-uniform 64-bit value kept as a value of its own in scalar registers
+ * (an empty asm: no instruction): hipcc does not fold it back into the
+ * expression it came from. */
+__device__ __forceinline__ int64_t scalar_value(int64_t v)
+{
+    __asm__("" : "+s"(v));
+    return v;
+}
+
+/* Running row pointer of a (rows x lanes) array walked one row at a time:
+ * a wave-uniform 64-bit pointer to the current row and a wave-uniform byte
+ * stride, so a step to the next or the previous row is ONE 64-bit scalar add
+ * where `base + stride * row` rebuilt a 64 x 64-bit scalar product (~7 SALU)
+ * for every access of an unrolled sweep.  Two empty asm statements (no
+ * instruction either) keep what hipcc would otherwise undo:
+ *   - on the pointer after each move: without it LLVM folds the unrolled adds
+ *     back into base + stride * constant, multiplies included;
+ *   - on the lane's 32-bit byte offset at each access: without it the
+ *     zero-extended offset is hoisted out of the block of the access, where
+ *     instruction selection no longer sees it as 32 bits, adds it to the row
+ *     pointer in a VGPR pair (v_lshl_add_u64) and addresses `off`.  With it
+ *     the access is SGPR base + 32-bit VGPR offset.
+ * The arrays are device memory (hipMalloc): the access names the global
+ * address space, which a pointer that went through an asm no longer implies.
+ * The cursor moves on every step of the wave, whether or not a lane's access
+ * is predicated off, and may stand before row 0 or past the last row; it is
+ * only dereferenced on a row of the array. */
+template <typename T>
+struct RowCursor {
+    typedef T __attribute__((address_space(1))) G;
+    typedef std::conditional_t<std::is_const<T>::value, const char, char> __attribute__((address_space(1))) GB;
+    T *row;               /* first element of the current row */
+    int64_t stride;       /* bytes between consecutive rows */
+    mutable uint32_t off; /* this lane's byte offset in a row */
+
+    __device__ __forceinline__ RowCursor() : row(nullptr), stride(0), off(0) {}
+    /* rows of `elems` elements, standing on row `row0`; the lane's element of a row is `lane` (< 2^29) */
+    __device__ __forceinline__ RowCursor(T *base, int64_t elems, int64_t row0, int64_t lane)
+    {
+        row = reinterpret_cast<T *>(wave_uniform(reinterpret_cast<int64_t>(base + elems * row0)));
+        stride = wave_uniform(elems * (int64_t)sizeof(T));
+        off = (uint32_t)lane * (uint32_t)sizeof(T);
+        pin();
+    }
+    __device__ __forceinline__ void pin() { __asm__("" : "+s"(row)); }
+    /* N = +1 / -1: to the next / the previous row */
+    template <int N>
+    __device__ __forceinline__ void advance()
+    {
+        static_assert(N == 1 || N == -1, "a row cursor moves one row at a time");
+        move(N > 0 ? stride : -stride);
+    }
+    /* by a wave-uniform number of bytes (a block of rows: a stride kept by the caller) */
+    __device__ __forceinline__ void move(int64_t bytes)
+    {
+        using B = std::conditional_t<std::is_const<T>::value, const char, char>;
+        row = reinterpret_cast<T *>(reinterpret_cast<B *>(row) + bytes);
+        pin();
+    }
+    /* the lane's element of the current row; o: the lane offset to use (a group of cursors shares one) */
+    __device__ __forceinline__ G *elem(uint32_t &o) const
+    {
+        __asm__("" : "+v"(o) : "s"(row));
+        return (G *)((GB *)row + o);
+    }
+    /* plain load (at(), get_tmp()), plain store (put_tmp()) and streaming store (put_out()) */
+    __device__ __forceinline__ T get() const { return *elem(off); }
+    __device__ __forceinline__ void put_tmp(T v) const { *elem(off) = v; }
+    __device__ __forceinline__ void put_out(T v) const { __builtin_nontemporal_store(v, elem(off)); }
+    __device__ __forceinline__ void put_out(T v, uint32_t &o) const { __builtin_nontemporal_store(v, elem(o)); }
+};
+
 /* Power-of-two renormalisation of a K-vector after every step: the largest
  * entry is brought into [0.5, 1) by an exact ldexp and the removed exponent
  * is accumulated in `ex`.  Keeping the max near 1 (rather than letting it
@@ -289,6 +372,47 @@ __device__ __forceinline__ void store_tk(double *out, const DevArgs &a, int64_t 
     for (int k = 0; k < K; ++k)
         put_out(out + a.P * ((int64_t)t + (int64_t)a.Tout * k), (uint32_t)p * 8u, v[k]);
 }
+
+/* Where a sweep's per-step [t, k] output rows go: TkIndexed rebuilds each row
+ * pointer from (t, k) as store_tk does; TkCursor keeps one RowCursor per state
+ * k and is stepped once per step of the sweep by its caller (advance<-1> in a
+ * backward sweep), t being implied by where the cursors stand. */
+struct TkIndexed {
+    template <int K>
+    __device__ __forceinline__ void store(double *out, const DevArgs &a, int64_t p, int t, const double (&v)[K]) const
+    {
+        store_tk<K>(out, a, p, t, v);
+    }
+    template <int N>
+    __device__ __forceinline__ void advance()
+    {
+    }
+};
+template <int K>
+struct TkCursor {
+    RowCursor<double> c[K];
+    mutable uint32_t off; /* pair p's byte offset, one for the K rows */
+    /* standing on step t of out[p, t, k] */
+    __device__ __forceinline__ TkCursor(double *out, const DevArgs &a, int64_t p, int t) : off((uint32_t)p * 8u)
+    {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            c[k] = RowCursor<double>(out, a.P, (int64_t)t + (int64_t)a.Tout * k, p);
+    }
+    __device__ __forceinline__ void store(double *, const DevArgs &, int64_t, int, const double (&v)[K]) const
+    {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            c[k].put_out(v[k], off);
+    }
+    template <int N>
+    __device__ __forceinline__ void advance()
+    {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            c[k].template advance<N>();
+    }
+};
 
 /* 1/x to ~1 ulp: v_rcp_f64 + two Newton steps (tolerance 1e-9 outputs only);
  * IEEE division for x below 2^-1000 where the reciprocal would overflow. */
@@ -388,6 +512,22 @@ __device__ __forceinline__ void vit_back_flush(const DevArgs &a, int64_t p, int 
             if (t < Tp)
                 put_out(a.zstar + a.P * (int64_t)t, (uint32_t)p * 4u, zb[u]);
         }
+    }
+}
+
+/* The same through a running row cursor over zstar that stands on the chunk's
+ * last step, t0 + CV - 1: the chunk's values go out last step first and the
+ * cursor is left on the step before the chunk, where a backtrack's next
+ * (earlier) chunk wants it. */
+template <int CV>
+__device__ __forceinline__ void vit_back_flush(RowCursor<int32_t> &zc, int Tp, int c, const int (&zb)[CV])
+{
+    const int t0 = c * CV;
+#pragma unroll
+    for (int u = CV - 1; u >= 0; --u) {
+        if (t0 + u < Tp)
+            zc.put_out((int32_t)zb[u]);
+        zc.template advance<-1>();
     }
 }
 

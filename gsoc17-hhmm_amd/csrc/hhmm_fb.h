@@ -35,11 +35,13 @@ __device__ __forceinline__ Obs unpack_obs(const uint32_t (&w)[kBigChunk / 8], in
 /* One kBigChunk-step block of the FB_BIG backward sweep: pass 1 recomputes
  * the block's forward states from its checkpoint keeping every kGroup-th;
  * pass 2 takes the groups from the end, recomputes each group's states and
- * walks it backwards (posteriors, beta step). */
-template <int MODEL, int K, int MODE, bool FULLB>
+ * walks it backwards (posteriors, beta step).  go: the gamma rows' addressing
+ * (TkIndexed, or a TkCursor standing on the block's last step t0 + B - 1: it
+ * is stepped back once per step, predicated off or not, and left on t0 - 1). */
+template <int MODEL, int K, int MODE, bool FULLB, typename GOUT>
 __device__ __forceinline__ void bwd_block_big(const DevArgs &a, const FbLane<MODEL, K> &ln, int t0,
                                               const uint32_t (&w)[kBigChunk / 8], const double (&ck)[K],
-                                              double (&be)[K], int &bex)
+                                              double (&be)[K], int &bex, GOUT &go)
 {
     constexpr int B = kBigChunk, G = kGroup, NG = B / G;
     double ga[NG][K];
@@ -94,10 +96,11 @@ __device__ __forceinline__ void bwd_block_big(const DevArgs &a, const FbLane<MOD
             if (r > 0)
                 emit_prob<MODEL, K>(ln.pp, ln.slab, ln.L, unpack_obs(w, r > 0 ? u - 1 : u), e2);
             if (FULLB || t < ln.Tp) {
-                emit_posteriors<K, MODE>(a, ln.p, t, gb[r], be, 0.0, 0.0);
+                emit_posteriors<K, MODE>(a, ln.p, t, gb[r], be, 0.0, 0.0, go);
                 if (t > ln.t0)
                     bwd_step<MODEL, K>(be, ln.pp, e1.e, unpack_obs(w, u), bex, u % fb_rp(MODE) == 0);
             }
+            go.template advance<-1>();
             e1 = e2;
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -127,13 +130,14 @@ __device__ __forceinline__ void fb_backward_big(const DevArgs &a, const FbLane<M
     };
     double ck[K], ckn[K];
     uint32_t w[NW], wn[NW];
+    TkIndexed go;
     load_blk(nblk - 1, ck, w);
     for (int blk = nblk - 1; blk >= 0; --blk) {
         load_blk(blk - 1, ckn, wn);
         if (blk < nfullb)
-            bwd_block_big<MODEL, K, MODE, true>(a, ln, blk * B, w, ck, be, bex);
+            bwd_block_big<MODEL, K, MODE, true>(a, ln, blk * B, w, ck, be, bex, go);
         else
-            bwd_block_big<MODEL, K, MODE, false>(a, ln, blk * B, w, ck, be, bex);
+            bwd_block_big<MODEL, K, MODE, false>(a, ln, blk * B, w, ck, be, bex, go);
 #pragma unroll
         for (int k = 0; k < K; ++k)
             ck[k] = ckn[k];

@@ -118,10 +118,12 @@ __device__ __forceinline__ void emit_alpha(const DevArgs &a, int64_t p, int t, c
     }
 }
 
-/* Outputs of step t once alpha_t and beta_t are known. */
-template <int K, int MODE>
+/* Outputs of step t once alpha_t and beta_t are known.  go: where the gamma
+ * profile's rows go (TkIndexed, or the caller's TkCursor standing on step t). */
+template <int K, int MODE, typename GOUT = TkIndexed>
 __device__ __forceinline__ void emit_posteriors(const DevArgs &a, int64_t p, int t, const double (&al)[K],
-                                                const double (&be)[K], double lsa, double lsb)
+                                                const double (&be)[K], double lsa, double lsb,
+                                                const GOUT &go = GOUT())
 {
     if constexpr (fb_base(MODE) == FB_GAMMA) {
         /* gamma = (alpha .* beta) / sum: the normalisations of alpha and beta
@@ -151,7 +153,7 @@ __device__ __forceinline__ void emit_posteriors(const DevArgs &a, int64_t p, int
 #pragma unroll
         for (int k = 0; k < K; ++k)
             ug[k] = ug[k] * r;
-        store_tk<K>(a.gamma, a, p, t, ug);
+        go.store(a.gamma, a, p, t, ug);
     } else {
         const uint32_t o = a.outputs;
         emit_alpha<K>(a, p, t, al, lsa);

@@ -74,12 +74,57 @@ __device__ __forceinline__ void fbv_backward(const DevArgs &a, const FbLane<MODE
     double ck[K], ckn[K];
     uint32_t w[NW], wn[NW], bw[CPB * WPC], bwn[CPB * WPC];
     load_blk(nblk - 1, ck, w, bw);
+    /* The sweep's per-step rows through running row pointers (RowCursor):
+     * gamma's K rows and zstar's row stand on the last step of the last block
+     * (past the series' end where T is no multiple of B: never stored there)
+     * and go back one row per step.  The per-block records stand on the block
+     * the loop prefetches next, max(blk - 1, 0): a block's rows are read going
+     * up from its first, then the cursor goes back one block while there is
+     * one.  Block nblk - 1 (above) keeps the indexed form: only its
+     * back-pointer rows can pass the last row and need the clamp -- with one
+     * block alone that block is also the one the loop re-reads, unused, so
+     * its back-pointer cursor then stays on row 0 (stride 0). */
+    TkCursor<K> go(a.gamma, a, p, nblk * B - 1);
+    RowCursor<int32_t> zc(a.zstar, a.P, (int64_t)nblk * B - 1, p);
+    const int64_t pb = max(nblk - 2, 0);
+    RowCursor<const double> ckc(a.ckpt, ln.Qs, pb * K, p);
+    RowCursor<const uint32_t> xkc(a.xpk, ln.Qs, pb * NW, p);
+    RowCursor<const uint32_t> bpc(a.bp, nblk >= 2 ? a.P : 0, pb * (CPB * WPC), p);
+    /* a block of each record in bytes, backwards */
+    const int64_t ck_blk = -ckc.stride * K, xk_blk = -xkc.stride * NW, bp_blk = -bpc.stride * (CPB * WPC);
+    auto load_prev = [&](int blk, double (&ck)[K], uint32_t (&w)[NW], uint32_t (&bw)[CPB * WPC]) {
+        /* each cursor ends one block up: back to its own block's first row, and on to the block's before it
+         * while the next iteration has one to prefetch, block blk - 2 (two moves: the choice between one
+         * block and two in one move comes out of hipcc as a product with the stride) */
+        const bool more = blk > 1;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            ck[k] = ckc.get();
+            ckc.template advance<1>();
+        }
+        ckc.move(ck_blk);
+        ckc.move(more ? ck_blk : 0);
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            w[i] = xkc.get();
+            xkc.template advance<1>();
+        }
+        xkc.move(xk_blk);
+        xkc.move(more ? xk_blk : 0);
+#pragma unroll
+        for (int i = 0; i < CPB * WPC; ++i) {
+            bw[i] = bpc.get();
+            bpc.template advance<1>();
+        }
+        bpc.move(bp_blk);
+        bpc.move(more ? bp_blk : 0);
+    };
     for (int blk = nblk - 1; blk >= 0; --blk) {
-        load_blk(blk - 1, ckn, wn, bwn);
+        load_prev(blk, ckn, wn, bwn);
         if (blk < nfullb)
-            bwd_block_big<MODEL, K, MODE, true>(a, ln, blk * B, w, ck, be, bex);
+            bwd_block_big<MODEL, K, MODE, true>(a, ln, blk * B, w, ck, be, bex, go);
         else
-            bwd_block_big<MODEL, K, MODE, false>(a, ln, blk * B, w, ck, be, bex);
+            bwd_block_big<MODEL, K, MODE, false>(a, ln, blk * B, w, ck, be, bex, go);
 #pragma unroll
         for (int cc = CPB - 1; cc >= 0; --cc) {
             const int cidx = blk * CPB + cc;
@@ -98,7 +143,7 @@ __device__ __forceinline__ void fbv_backward(const DevArgs &a, const FbLane<MODE
                     for (int u = 0; u < C; ++u)
                         zb[u] = 0;
                 }
-                vit_back_flush<C, false>(a, p, Tp, cidx, zb);
+                vit_back_flush<C>(zc, Tp, cidx, zb);
             }
         }
 #pragma unroll
@@ -294,7 +339,6 @@ __device__ __forceinline__ void vfb_viterbi(const DevArgs &a, int64_t p, const P
             xcheck_acc<CV, decltype(full)::value>(xm, cur, c, Tp);
         }
     };
-    const std::true_type full;
     const std::false_type tail;
     Obs cur[CV];
     load_chunk<MODEL, CV, false>(cur, sp, 0);
@@ -313,16 +357,35 @@ __device__ __forceinline__ void vfb_viterbi(const DevArgs &a, int64_t p, const P
     vit_fwd_chunk<MODEL, K, CV, false, true>(a, p, pp, slab, Tp, 0, cur, grp[0][0], le, dl, word);
     pack_put(0, cur, tail);
     int c = 1;
-    for (; c + D <= nfull; c += D) {
+    /* The group loop's rows through running row pointers (RowCursor): x's rows
+     * of the group it prefetches, the packed-symbol row and the back-pointer
+     * word rows of the chunks it runs, each one row further per access.  A
+     * cursor cannot clamp, so the loop runs while the whole prefetched group
+     * lies inside x's Tmax rows; the (at most 2 D) full chunks after that go
+     * chunk by chunk below with the clamped loads. */
+    RowCursor<const int32_t> xc(sp.x, sp.stride, (1 + D) * CV, sp.n);
+    RowCursor<uint32_t> pkc(a.xpk, a.P, 1, p);
+    BpCursor wo(a, p, CV / bp_steps_per_word(K));
+    for (; c + D <= nfull && (c + 2 * D) * CV <= sp.tmax; c += D) {
         Obs nxt[D][CV];
 #pragma unroll
         for (int i = 0; i < D; ++i)
-            load_chunk<MODEL, CV, false>(nxt[i], sp, (c + D + i) * CV);
+#pragma unroll
+            for (int u = 0; u < CV; ++u) {
+                nxt[i][u].x = xc.get();
+                nxt[i][u].aux = 0;
+                nxt[i][u].xr = 0.0;
+                xc.template advance<1>();
+            }
 #pragma unroll
         for (int i = 0; i < D; ++i) {
             vit_fwd_chunk<MODEL, K, CV, true>(a, p, pp, slab, Tp, c + i, grp[i],
-                                              (i + 1 < D) ? grp[i + 1 < D ? i + 1 : 0][0] : nxt[0][0], le, dl, word);
-            pack_put(c + i, grp[i], full); /* c + i < nfull: every lane's steps are < Tp */
+                                              (i + 1 < D) ? grp[i + 1 < D ? i + 1 : 0][0] : nxt[0][0], le, dl, word,
+                                              wo);
+            /* c + i < nfull: every lane's steps are < Tp */
+            pkc.put_tmp(pack_chunk<MODEL, K>(grp[i]));
+            pkc.template advance<1>();
+            xcheck_acc<CV, true>(xm, grp[i], c + i, Tp);
         }
 #pragma unroll
         for (int i = 0; i < D; ++i)

@@ -94,11 +94,36 @@ __device__ __forceinline__ void vit_step(double (&dl)[K], const PairParams<MODEL
         dl[j] = nd[j];
 }
 
-template <int MODEL, int K, int CV, bool FULLC, bool FIRST = false>
+/* Where a chunk's finished back-pointer words go: BpIndexed rebuilds the row
+ * pointer from the word's row; BpCursor is a running row pointer that stands
+ * on the next word's row and moves on with every word -- for chunks every lane
+ * of the wave runs in full (FULLC) only, where each word is stored by the
+ * whole wave, so the cursor's moves stay wave-uniform. */
+struct BpIndexed {
+    static constexpr bool kUniformOnly = false;
+    __device__ __forceinline__ void put(const DevArgs &a, int64_t p, int row, uint32_t word)
+    {
+        put_tmp(a.bp + a.P * (int64_t)row, (uint32_t)p * 4u, word);
+    }
+};
+struct BpCursor {
+    static constexpr bool kUniformOnly = true;
+    RowCursor<uint32_t> c;
+    __device__ __forceinline__ BpCursor(const DevArgs &a, int64_t p, int row) : c(a.bp, a.P, row, p) {}
+    __device__ __forceinline__ void put(const DevArgs &, int64_t, int, uint32_t word)
+    {
+        c.put_tmp(word);
+        c.advance<1>();
+    }
+};
+
+template <int MODEL, int K, int CV, bool FULLC, bool FIRST = false, typename WOUT>
 __device__ __forceinline__ void vit_fwd_chunk(const DevArgs &a, int64_t p, const PairParams<MODEL, K> &pp,
                                               const double2 *slab, int Tp, int c, const Obs (&cur)[CV],
-                                              const Obs &nxt0, double (&le)[K], double (&dl)[K], uint32_t &word)
+                                              const Obs &nxt0, double (&le)[K], double (&dl)[K], uint32_t &word,
+                                              WOUT &wo)
 {
+    static_assert(FULLC || !WOUT::kUniformOnly, "a word cursor needs chunks the whole wave runs in full");
     constexpr int SPW = bp_steps_per_word(K);
     const int t0 = c * CV;
 #pragma unroll
@@ -113,7 +138,7 @@ __device__ __forceinline__ void vit_fwd_chunk(const DevArgs &a, int64_t p, const
             else if (!(FIRST && u == 0))
                 vit_step<MODEL, K, false>(dl, pp, le, cur[u], word, u % SPW);
             if (u % SPW == SPW - 1) {
-                put_tmp(a.bp + a.P * (int64_t)(t / SPW), (uint32_t)p * 4u, word);
+                wo.put(a, p, t / SPW, word);
                 word = 0;
             }
         }
@@ -121,6 +146,14 @@ __device__ __forceinline__ void vit_fwd_chunk(const DevArgs &a, int64_t p, const
         for (int k = 0; k < K; ++k)
             le[k] = ln[k];
     }
+}
+template <int MODEL, int K, int CV, bool FULLC, bool FIRST = false>
+__device__ __forceinline__ void vit_fwd_chunk(const DevArgs &a, int64_t p, const PairParams<MODEL, K> &pp,
+                                              const double2 *slab, int Tp, int c, const Obs (&cur)[CV],
+                                              const Obs &nxt0, double (&le)[K], double (&dl)[K], uint32_t &word)
+{
+    BpIndexed wo;
+    vit_fwd_chunk<MODEL, K, CV, FULLC, FIRST>(a, p, pp, slab, Tp, c, cur, nxt0, le, dl, word, wo);
 }
 
 /* One workgroup of the Viterbi decoder: pairs [block * blockDim, +blockDim).

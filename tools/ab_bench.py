@@ -10,7 +10,8 @@ HHMM_PROBE_*_LDS_KB occupancy probes of the launch templates in hhmm_hmm.h)
 Each variant runs the bench.py C2 step (fb_kernel, then viterbi_kernel, then
 the two concurrently on two streams as bench.py does: "pair") on
 the same resident inputs; rounds are interleaved A B C A B C ...; per-kernel
-HIP-event times are reported as median / min over rounds.  Variants also
+HIP-event times are reported as median / min / max over rounds and round by
+round ("all_ms": round r of every variant ran back to back).  Variants also
 cross-check each other's outputs (gamma within 1e-12, zstar exact).
 """
 import argparse
@@ -117,7 +118,8 @@ def main():
                     print(f"{n}: split vs step outputs identical: gamma {same_g}, zstar {same_z}", flush=True)
     out = {}
     for n, t in times.items():
-        out[n] = {k: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v))} for k, v in t.items()}
+        out[n] = {k: {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)), "max_ms": float(np.max(v)),
+                      "all_ms": [round(x, 3) for x in v]} for k, v in t.items()}
         print(n, json.dumps(out[n]), flush=True)
     print(json.dumps(out))
 
