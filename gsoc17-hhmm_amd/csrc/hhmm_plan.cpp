@@ -88,6 +88,66 @@ ScanPlan scan_plan(int model, int K, int Tmax, int64_t P, uint32_t outputs, uint
     return sp;
 }
 
+ScanPlan estep_scan_plan(int model, int K, int, int Tmax, int64_t P, uint32_t flags)
+{
+    ScanPlan sp{0, 0};
+    if (!hmm_has_backward(model) || K < 1 || K > kMaxK || (model == HHMM_MODEL_TAYAL && K != 4) || Tmax < 1 || P < 1 ||
+        (flags & HHMM_FLAG_SCAN_OFF))
+        return sp;
+    /* the gate of scan_plan at large K, borrowed: under 4096 pairs the lane
+     * kernel leaves SIMDs idle, and from 8192 steps on a series is long enough
+     * to pay for phases 1-2 */
+    if (!(flags & HHMM_FLAG_SCAN_FORCE) && !(P < kEstepScanMaxP && Tmax >= kEstepScanMinT))
+        return sp;
+    const int C = fb_chunk(K);
+    const int log2cl = (int)((flags >> 8) & 0xffu);
+    int cl;
+    if (log2cl > 0) {
+        cl = 1 << std::min(log2cl, 30);
+    } else {
+        cl = 4 * C;
+        while (P * (((int64_t)Tmax + cl - 1) / cl) > kEstepScanLanes && cl < (1 << 20))
+            cl *= 2;
+    }
+    cl = std::max(C, cl - cl % C);
+    const int64_t nc = ((int64_t)Tmax + cl - 1) / cl;
+    if (P * scan_lanes_per_chunk(nc) >= (int64_t(1) << 29)) /* checkpoint columns are 32-bit byte offsets */
+        return sp;
+    sp.cl = cl;
+    sp.nc = (int)nc;
+    return sp;
+}
+
+EstepScanLayout estep_scan_layout(int model, int K, int L, int Tmax, int64_t P, uint32_t flags)
+{
+    EstepScanLayout w{};
+    w.sp = estep_scan_plan(model, K, L, Tmax, P, flags);
+    if (w.sp.cl == 0)
+        return w;
+    const size_t d = sizeof(double), nc = (size_t)w.sp.nc, k = (size_t)K, p = (size_t)P;
+    w.ncw = scan_lanes_per_chunk(w.sp.nc);
+    w.nwp = w.ncw / 64;
+    w.G = P * w.ncw;
+    w.ns = K + K * K + (model == HHMM_MODEL_HMM_GAUSS ? 3 * K : K * L);
+    size_t off = 0;
+    auto take = [&](size_t bytes) {
+        const size_t o = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return o;
+    };
+    w.mf = take(nc * k * k * p * d);
+    w.mx = take(nc * 3 * p * d);
+    w.st = take(nc * k * p * d);
+    w.sl = take(nc * p * d);
+    w.be = take(nc * k * p * d);
+    w.bl = take(nc * p * d);
+    w.ckpt = take((size_t)(w.sp.cl / fb_chunk(K)) * k * (size_t)w.G * d);
+    w.part = take(p * (size_t)w.nwp * (size_t)(w.ns + kEstepScanTail) * d);
+    w.pa = take(p * k * k * d);
+    w.total = off;
+    return w;
+}
+
 int lkm_plan(int model, int K, int64_t N, int pairing, uint32_t outputs, uint32_t flags, int scan_cl)
 {
     if (model != HHMM_MODEL_HMM_MULTINOM || K <= kMaxK || K > kMaxKLarge || pairing != HHMM_PAIR_GRID || N < 16 ||

@@ -72,6 +72,40 @@ struct ScanPlan {
 };
 ScanPlan scan_plan(int model, int K, int Tmax, int64_t P, uint32_t outputs, uint32_t flags);
 
+/* The E-step and the expected statistics as a parallel scan over T
+ * (hhmm_estep_scan.hip), hmm, hmm-multinom, hmm-multinom-semisup and
+ * hhmm-tayal2009 at K <= kMaxK: T-chunk length and count (cl = 0: the
+ * sequential lane kernel).  HHMM_FLAG_SCAN_CHUNK_LOG2(n) gives the length
+ * (rounded down to a multiple of fb_chunk(K), at least one), HHMM_FLAG_SCAN_FORCE
+ * passes the gate, HHMM_FLAG_SCAN_OFF closes it.  Left alone the scan runs
+ * where P < kEstepScanMaxP and Tmax >= kEstepScanMinT, with chunks of
+ * 4 fb_chunk(K) steps doubled until P * nc <= kEstepScanLanes: that bounds the
+ * phase-3 lanes (one per (pair, chunk), a pair's chunks padded to whole waves:
+ * at most kEstepScanLanes + 63 P while chunks stay under 2^20 steps, where the
+ * doubling stops) and with them the partials, one record per wave.  Off where the padded lanes reach 2^29 (checkpoint columns are 32-bit
+ * byte offsets), whatever the flags. */
+constexpr int64_t kEstepScanMaxP = 4096;
+constexpr int kEstepScanMinT = 8192;
+constexpr int64_t kEstepScanLanes = 262144;
+ScanPlan estep_scan_plan(int model, int K, int L, int Tmax, int64_t P, uint32_t flags);
+
+/* Workspace of a T-scan E-step, in this order, every region at a 256-byte
+ * boundary, all fp64 (include/hhmm_estep.h documents it): the scan regions of
+ * DevArgs (sc_mf [P][nc][K][K], sc_mx [P][nc][3], sc_st [nc][K][P], sc_sl
+ * [nc][P], sc_be [nc][K][P], sc_bl [nc][P]; no sc_qb), the in-chunk checkpoints
+ * [cl / fb_chunk(K)][K][G] over G = P * ncw phase-3 lanes (ncw: nc rounded up
+ * to whole waves), the partials [P][nwp][ns + kEstepScanTail] (nwp = ncw / 64
+ * waves per pair; ns = K + K^2 + K L statistics, 3 K in place of K L for the
+ * Gaussian hmm) and each pair's A, [P][K][K].  total = 0: no scan (estep_scan_plan). */
+constexpr int kEstepScanTail = 5; /* bad, max x - 1, max aux - 1, aux_1, x_1 */
+struct EstepScanLayout {
+    ScanPlan sp;
+    int64_t ncw, nwp, G;
+    int ns;
+    size_t mf, mx, st, sl, be, bl, ckpt, part, pa, total;
+};
+EstepScanLayout estep_scan_layout(int model, int K, int L, int Tmax, int64_t P, uint32_t flags);
+
 /* T-parallel exact Viterbi (hhmm_vscan.h): V-chunks of kVsChunk steps (a whole
  * number of back-pointer words at K = 2 and 4); returns the chunk count per
  * pair of a Viterbi over Tv steps, 0 when the sequential decoders run. */

@@ -441,7 +441,10 @@ constexpr int kBoundWaves = HHMM_BOUND_WAVES;
 #define HHMM_BOUND_SHORT 1
 #endif
 
-template <int K, bool BW>
+/* ADJ (backward only): the maps are the FORWARD chunk products, beta_{t-1} =
+ * F_t beta_t -- the adjoint of the forward pass, which the E-step sweeps
+ * (hhmm_estep_scan.hip): sc_mf with its exponent, and no sc_qb at all. */
+template <int K, bool BW, bool ADJ = false>
 __device__ __forceinline__ void bound_walk(const DevArgs &a, int64_t p, int ncp, int c0, int n, double (&v)[K],
                                            double &vsc, RowMat<K> *tot)
 {
@@ -451,10 +454,10 @@ __device__ __forceinline__ void bound_walk(const DevArgs &a, int64_t p, int ncp,
         return;
     const int nw = one ? 1 : kBoundWaves;
     const int lo = (int)((int64_t)n * wave / nw), hi = (int)((int64_t)n * (wave + 1) / nw);
-    const double *base = BW ? a.sc_qb : a.sc_mf;
+    const double *base = (BW && !ADJ) ? a.sc_qb : a.sc_mf;
     auto chunk = [&](int i) { return BW ? ncp - 1 - i : c0 + i; };
     auto fetch = [&](int ib, RawMat<K> &r) { /* item ib + lane, clamped into the range */
-        rawmat_fetch<K, BW>(base, a, chunk(max(min(ib + lane, hi - 1), 0)), p, BW ? 2 : 0, r);
+        rawmat_fetch<K, BW>(base, a, chunk(max(min(ib + lane, hi - 1), 0)), p, (BW && !ADJ) ? 2 : 0, r);
     };
     RawMat<K> nx;
     if (!one) {
@@ -528,8 +531,9 @@ __device__ __forceinline__ void bound_walk(const DevArgs &a, int64_t p, int ncp,
 /* One workgroup of kBoundWaves waves per (pair, direction): blockIdx.y == 0
  * the forward walk (f entering chunks c0 .. ncp-1, the loglik), 1 the
  * backward walk (beta leaving chunks ncp-1 .. 0; chunk c's map applied to a
- * row vector is Q_c^T).  The two are independent. */
-template <int MODEL, int K, bool BWD>
+ * row vector is Q_c^T).  The two are independent.  ADJ: the backward walk takes
+ * the forward products (bound_walk). */
+template <int MODEL, int K, bool BWD, bool ADJ = false>
 __global__ void __launch_bounds__(64 * kBoundWaves) scan_bound_kernel(const DevArgs a)
 {
     __shared__ RowMat<K> tot[kBoundWaves];
@@ -589,7 +593,7 @@ __global__ void __launch_bounds__(64 * kBoundWaves) scan_bound_kernel(const DevA
         }
         if (t0)
             a.sc_bl[p + a.P * (int64_t)(ncp - 1)] = bsc;
-        bound_walk<K, true>(a, p, ncp, 0, max(ncp - 1, 0), b, bsc, tot);
+        bound_walk<K, true, ADJ>(a, p, ncp, 0, max(ncp - 1, 0), b, bsc, tot);
     }
 }
 

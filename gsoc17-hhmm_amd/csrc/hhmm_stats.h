@@ -10,7 +10,7 @@
  * (hhmm_psis.hip).  The
  * kernels differ; the argument checks, the DevArgs of a launch, the LDS fit,
  * the dispatch on K and the launch epilogue do not.  stats_check_tail belongs
- * to the six entries that fill an hhmm_estep_result; the IOHMM E-step and the
+ * to the eight entries that fill an hhmm_estep_result; the IOHMM E-step and the
  * pointwise densities have a result struct and a tail of their own.  Not part of the public ABI.
  */
 #pragma once
@@ -27,7 +27,7 @@
 
 namespace hhmm {
 
-/* Each of the eleven entries gives the host path of hhmm_stats_api.cpp
+/* Each of the thirteen entries gives the host path of hhmm_stats_api.cpp
  * (StatsEntry, stats_*) a check_* and a launch_*; what those share follows them.
  *
  * Batched E-step (hhmm_estep.hip): argument checks (no device needed), the
@@ -66,6 +66,21 @@ hhmm_status launch_draw_stats_large(const hhmm_request *r, const hhmm_estep_resu
 hhmm_status check_expected_stats(const hhmm_request *r, const hhmm_estep_result *o);
 hhmm_status launch_expected_stats(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
                                   hipStream_t st);
+
+/* The E-step and the expected statistics as a parallel scan over T
+ * (hhmm_estep_scan.hip; the checks sit beside their sequential twins in
+ * hhmm_estep.hip and share their scope and LDS fit): argument checks (no device
+ * needed), the workspace of EstepScanLayout and the one launch of both entries
+ * on `st` (device pointers).  estep_waves: the lane kernels' waves per
+ * workgroup and its LDS (two tables per wave for the discrete programs, xi for
+ * the Gaussian kernels at K >= 7); 0: one wave's tables do not fit. */
+inline constexpr const char *kEstepScanAbove = "hhmm_estep_large takes hmm and hmm-multinom at 8 < K <= 32";
+hhmm_status check_estep_scan(const hhmm_request *r, const hhmm_estep_result *o);
+hhmm_status check_expected_stats_scan(const hhmm_request *r, const hhmm_estep_result *o);
+int estep_waves(int model, int K, int L, size_t *lds);
+size_t estep_scan_workspace_bytes(const hhmm_request *r, int64_t P);
+hhmm_status launch_estep_scan(const hhmm_request *r, const hhmm_estep_result *res, int64_t P, void *ws,
+                              hipStream_t st);
 
 /* IOHMM E-step (hhmm_estep_io.hip): argument checks (no device needed) and the
  * launch on `st` (device pointers); its own result struct, no workspace. */
@@ -106,11 +121,15 @@ hhmm_status launch_psis_lfo(const hhmm_request *r, const hhmm_psis_result *res, 
  * entry's scope (`scope` says which models it takes and where the others go),
  * K, HHMM_DEVICE_SET.  `entry`: the entry's name in messages.  k_lo..k_hi: the
  * K the entry's kernel takes (the lane-per-pair kernels' 1..kMaxK unless given);
- * `below`: the entry a message names for K < k_lo. */
-inline hhmm_status stats_check_k(const char *entry, int K, int k_lo, int k_hi, const char *below = "hhmm_estep")
+ * `below`: the entry a message names for K < k_lo; `above`: where given, what a
+ * message says of K > k_hi (the entry that takes it). */
+inline hhmm_status stats_check_k(const char *entry, int K, int k_lo, int k_hi, const char *below = "hhmm_estep",
+                                 const char *above = nullptr)
 {
     if (K > k_hi) {
-        if (k_hi == kMaxK)
+        if (above)
+            set_error("%s: K = %d, the kernel supports K <= %d (%s)", entry, K, k_hi, above);
+        else if (k_hi == kMaxK)
             set_error("%s: K = %d, the lane-per-pair kernel supports K <= %d", entry, K, kMaxK);
         else
             set_error("%s: K = %d, the state-parallel kernel supports %d <= K <= %d", entry, K, k_lo, k_hi);
@@ -125,7 +144,8 @@ inline hhmm_status stats_check_k(const char *entry, int K, int k_lo, int k_hi, c
 }
 
 inline hhmm_status stats_check_head(const char *entry, const hhmm_request *r, bool (*model_ok)(int), const char *scope,
-                                    int k_lo = 1, int k_hi = kMaxK, const char *below = "hhmm_estep")
+                                    int k_lo = 1, int k_hi = kMaxK, const char *below = "hhmm_estep",
+                                    const char *above = nullptr)
 {
     if (!r) {
         set_error("%s: request must be non-NULL", entry);
@@ -143,7 +163,7 @@ inline hhmm_status stats_check_head(const char *entry, const hhmm_request *r, bo
         set_error("%s: model %d is not supported (%s)", entry, r->model, scope);
         return HHMM_ERR_UNSUPPORTED;
     }
-    if (stats_check_k(entry, r->data.K, k_lo, k_hi, below) != HHMM_OK)
+    if (stats_check_k(entry, r->data.K, k_lo, k_hi, below, above) != HHMM_OK)
         return HHMM_ERR_UNSUPPORTED;
     if (r->device == HHMM_DEVICE_SET) {
         set_error("%s: HHMM_DEVICE_SET is not supported (one device per call)", entry);

@@ -1,6 +1,6 @@
 /*
  * hhmm_stats_api.cpp -- the C ABI of the statistics per (series, draw) pair:
- * the E-step (include/hhmm_estep.h), the draw statistics (hhmm_gibbs.h,
+ * the E-step (include/hhmm_estep.h; its T-scan, hhmm_estep_scan.hip, too), the draw statistics (hhmm_gibbs.h,
  * hhmm_gibbs_gauss.h), the expected draw statistics (hhmm_expect.h), the IOHMM
  * E-step (hhmm_estep_io.h), the pointwise predictive densities
  * (hhmm_pointwise.h) and PSIS-LOO / -LFO on top of them (hhmm_psis.h).  They
@@ -53,6 +53,7 @@ struct StatsEntry {
                    std::vector<StatsArr> &arrs);
     int k_lo = 1, k_hi = kMaxK;       /* the K its kernel takes (stats_check_k) */
     const char *below = "hhmm_estep"; /* the entry that takes K < k_lo */
+    const char *above = nullptr;      /* where given: what a message says of K > k_hi */
 };
 
 /* The row of a state-parallel entry: its name, its uniforms and its K from its scope (hhmm_stats.h). */
@@ -233,6 +234,27 @@ static const StatsEntry kExpectedStats = {"expected statistics",
                                           typed_launch<hhmm_estep_result, launch_expected_stats>,
                                           estep_workspace,
                                           estep_arrays};
+/* the T-scan of both (hhmm_estep_scan.hip): one launch and one workspace, the checks of their twins */
+static const StatsEntry kEstepScan = {"T-scan E-step",
+                                      false,
+                                      typed_check<hhmm_estep_result, check_estep_scan>,
+                                      typed_launch<hhmm_estep_result, launch_estep_scan>,
+                                      estep_scan_workspace_bytes,
+                                      estep_arrays,
+                                      1,
+                                      kMaxK,
+                                      "hhmm_estep",
+                                      kEstepScanAbove};
+static const StatsEntry kExpectedStatsScan = {"T-scan expected statistics",
+                                              false,
+                                              typed_check<hhmm_estep_result, check_expected_stats_scan>,
+                                              typed_launch<hhmm_estep_result, launch_estep_scan>,
+                                              estep_scan_workspace_bytes,
+                                              estep_arrays,
+                                              1,
+                                              kMaxK,
+                                              "hhmm_estep",
+                                              kEstepScanAbove};
 static const StatsEntry kPointwise = {"pointwise",
                                       false,
                                       typed_check<hhmm_pointwise_result, check_pointwise>,
@@ -294,7 +316,7 @@ static hhmm_status stats_workspace_size(const StatsEntry &en, const hhmm_request
         set_error("request describes no pairs");
         return HHMM_ERR_INVALID_ARGUMENT;
     }
-    if (stats_check_k(en.name, req->data.K, en.k_lo, en.k_hi, en.below) != HHMM_OK)
+    if (stats_check_k(en.name, req->data.K, en.k_lo, en.k_hi, en.below, en.above) != HHMM_OK)
         return HHMM_ERR_UNSUPPORTED;
     *bytes = en.workspace(req, P);
     return HHMM_OK;
@@ -405,6 +427,46 @@ hhmm_status hhmm_estep_large_device(const hhmm_request *req, hhmm_estep_result *
 hhmm_status hhmm_estep_large(const hhmm_request *req, hhmm_estep_result *res)
 {
     return stats_host(kEstepLarge, req, res);
+}
+
+hhmm_status hhmm_estep_scan_workspace_size(const hhmm_request *req, size_t *bytes)
+{
+    return stats_workspace_size(kEstepScan, req, bytes);
+}
+hhmm_status hhmm_estep_scan_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                                   size_t workspace_bytes_, void *stream)
+{
+    return stats_device(kEstepScan, req, res, workspace, workspace_bytes_, stream);
+}
+hhmm_status hhmm_estep_scan(const hhmm_request *req, hhmm_estep_result *res)
+{
+    return stats_host(kEstepScan, req, res);
+}
+hhmm_status hhmm_estep_scan_plan(const hhmm_request *req, int32_t *chunk_len, int32_t *n_chunks)
+{
+    if (!req || !chunk_len || !n_chunks || npairs(req) < 1) {
+        set_error("NULL argument, or a request that describes no pairs");
+        return HHMM_ERR_INVALID_ARGUMENT;
+    }
+    const ScanPlan sp = estep_scan_plan(req->model, req->data.K, req->data.L, req->data.T_max, npairs(req),
+                                        (uint32_t)req->flags);
+    *chunk_len = sp.cl;
+    *n_chunks = sp.nc;
+    return HHMM_OK;
+}
+
+hhmm_status hhmm_expected_stats_scan_workspace_size(const hhmm_request *req, size_t *bytes)
+{
+    return stats_workspace_size(kExpectedStatsScan, req, bytes);
+}
+hhmm_status hhmm_expected_stats_scan_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                                            size_t workspace_bytes_, void *stream)
+{
+    return stats_device(kExpectedStatsScan, req, res, workspace, workspace_bytes_, stream);
+}
+hhmm_status hhmm_expected_stats_scan(const hhmm_request *req, hhmm_estep_result *res)
+{
+    return stats_host(kExpectedStatsScan, req, res);
 }
 
 hhmm_status hhmm_draw_stats_workspace_size(const hhmm_request *req, size_t *bytes)

@@ -398,6 +398,15 @@ def declare(lib):
     lib.hhmm_estep_large_device.restype = C.c_int
     lib.hhmm_estep_large.argtypes = [RP, EP]
     lib.hhmm_estep_large.restype = C.c_int
+    # the same header: the E-step as a parallel scan over T, and the schedule "auto" follows
+    lib.hhmm_estep_scan_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
+    lib.hhmm_estep_scan_workspace_size.restype = C.c_int
+    lib.hhmm_estep_scan_device.argtypes = [RP, EP, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.hhmm_estep_scan_device.restype = C.c_int
+    lib.hhmm_estep_scan.argtypes = [RP, EP]
+    lib.hhmm_estep_scan.restype = C.c_int
+    lib.hhmm_estep_scan_plan.argtypes = [RP, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.hhmm_estep_scan_plan.restype = C.c_int
     # include/hhmm_gibbs.h (the result struct is the E-step's)
     lib.hhmm_draw_stats_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
     lib.hhmm_draw_stats_workspace_size.restype = C.c_int
@@ -426,6 +435,12 @@ def declare(lib):
     lib.hhmm_expected_stats_device.restype = C.c_int
     lib.hhmm_expected_stats.argtypes = [RP, EP]
     lib.hhmm_expected_stats.restype = C.c_int
+    lib.hhmm_expected_stats_scan_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]
+    lib.hhmm_expected_stats_scan_workspace_size.restype = C.c_int
+    lib.hhmm_expected_stats_scan_device.argtypes = [RP, EP, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.hhmm_expected_stats_scan_device.restype = C.c_int
+    lib.hhmm_expected_stats_scan.argtypes = [RP, EP]
+    lib.hhmm_expected_stats_scan.restype = C.c_int
     # include/hhmm_estep_io.h
     IP = C.POINTER(EstepIoResult)
     lib.hhmm_estep_io_workspace_size.argtypes = [RP, C.POINTER(C.c_size_t)]

@@ -14,7 +14,7 @@ from .estep import FIT_MODELS, MODELS, estep, m_step
 from .expect import expected_stats
 
 
-def baum_welch(model, data, init, n_iter, pairing="zip", device=-1, lib=None):
+def baum_welch(model, data, init, n_iter, pairing="zip", device=-1, lib=None, schedule="auto", flags=0):
     """n_iter EM iterations from the per-pair parameters `init`.
 
     init: {name: (P, ...)} draw arrays as estep() / expected_stats() take them
@@ -22,7 +22,9 @@ def baum_welch(model, data, init, n_iter, pairing="zip", device=-1, lib=None):
     series).  Returns (params, trace): the parameters after the last M-step
     and the (n_iter, P) log-likelihoods of the parameters each iteration
     started from -- under exact arithmetic a non-decreasing sequence per pair.
-    hmm and hmm-multinom at K <= 32 (hhmm_estep_large above 8).
+    hmm and hmm-multinom at K <= 32 (hhmm_estep_large above 8).  schedule and
+    flags go to every E-step (estep(): "scan" runs it in parallel over T, for
+    one or a few long series).
     A pair whose log-likelihood is not finite keeps NaN parameters from then
     on."""
     if model not in FIT_MODELS:
@@ -34,7 +36,7 @@ def baum_welch(model, data, init, n_iter, pairing="zip", device=-1, lib=None):
     params = {k: np.array(v, dtype=np.float64) for k, v in init.items()}
     trace = []
     for _ in range(int(n_iter)):
-        stats = e_step(model, data, params, pairing, device, lib)
+        stats = e_step(model, data, params, pairing, device, lib, schedule=schedule, flags=flags)
         trace.append(np.array(stats["loglik"]))
         params = m_step(model, stats, params)
     return params, np.array(trace).reshape(int(n_iter), -1)

@@ -14,7 +14,11 @@ The statistics follow the CODED likelihood of each Stan program: hmm.stan:30
 adds sum_k normal_lpdf(x_1 | mu_k, sigma_k) to every state at t = 1 (quirk Q2),
 so x_1 enters w_k / s1_k / s2_k with weight 1 for every state.  hmm and
 hmm-multinom at K <= 32: hhmm_estep up to K = 8 (a lane per pair),
-hhmm_estep_large above (a group of 16 or 32 lanes per pair).
+hhmm_estep_large above (a group of 16 or 32 lanes per pair).  One or a few long
+series (an EM fit of one long series from a handful of starts) leave a
+lane-per-pair kernel one lane each for T dependent steps: `schedule="scan"`
+runs the same E-step in parallel over T (hhmm_estep_scan, K <= 8), and
+`schedule="auto"`, the default, takes it where the library's plan does.
 
 score() and m_step() also take the statistics hhmm_amd.expected_stats returns
 for the two masked programs (FIT_MODELS): hmm-multinom-semisup with the
@@ -23,19 +27,53 @@ p_11, the two rows of A_row and phi_k.
 """
 import numpy as np
 
-from . import _stats
+from . import _abi, _stats
 from .api import load_library
 
 MODELS = ("hmm", "hmm-multinom")
 FIT_MODELS = MODELS + ("hmm-multinom-semisup", "hhmm-tayal2009")  # score / m_step / baum_welch
 _TINY = 1e-300
 MAX_K_LANE = 8  # hhmm_estep: the lane-per-pair kernel (csrc kMaxK)
+SCHEDULES = ("auto", "lanes", "scan")
+SCAN_MAX_P = 4096  # schedule="auto": the scan only under this many pairs ... (csrc kEstepScanMaxP)
+SCAN_MIN_T = 8192  # ... and from this T_max on (csrc kEstepScanMinT)
 
 
-def entry_name(K):
+def entry_name(K, schedule="lanes"):
     """The library entry estep() calls at K states: "estep" up to MAX_K_LANE,
-    "estep_large" above (K > 32 reaches the library, which rejects it)."""
+    "estep_large" above (K > 32 reaches the library, which rejects it); under
+    the resolved schedule "scan" (K <= MAX_K_LANE only), "estep_scan"."""
+    if schedule == "scan":
+        return "estep_scan"
     return "estep" if int(K) <= MAX_K_LANE else "estep_large"
+
+
+def resolve_schedule(pr, schedule="auto", lib=None):
+    """"lanes" or "scan": the schedule estep() and expected_stats() run a prepared request on.
+
+    "lanes" is the kernel that walks every series step by step.  "scan" is the
+    parallel scan over T: K <= MAX_K_LANE, else a ValueError that names
+    estep_large.  "auto" takes the scan only when K <= MAX_K_LANE, P <
+    SCAN_MAX_P and T_max >= SCAN_MIN_T (or pr's flags force it) and the
+    library's plan (hhmm_estep_scan_plan, no device needed) chooses it; a
+    request outside that gate is "lanes" without a call into the library."""
+    if schedule not in SCHEDULES:
+        raise ValueError(f"schedule must be one of {SCHEDULES}, not {schedule!r}")
+    if schedule == "lanes":
+        return "lanes"
+    if schedule == "scan":
+        if pr.K > MAX_K_LANE:
+            raise ValueError(f"schedule='scan' covers K <= {MAX_K_LANE}; K = {pr.K} goes to estep_large "
+                             "(schedule='lanes' or 'auto')")
+        return "scan"
+    forced = bool(int(pr.req.flags) & _abi.FLAG_SCAN_FORCE)
+    if pr.K > MAX_K_LANE or not (forced or (pr.P < SCAN_MAX_P and pr.Tmax >= SCAN_MIN_T)):
+        return "lanes"
+    import ctypes as C
+    cl, nc = C.c_int32(0), C.c_int32(0)
+    if (lib or load_library()).hhmm_estep_scan_plan(C.byref(pr.req), C.byref(cl), C.byref(nc)) < 0:
+        return "lanes"
+    return "scan" if cl.value > 0 else "lanes"
 
 
 def stat_shapes(model, P, K, L):
@@ -62,8 +100,13 @@ def prepare(model, data, draws, pairing="grid", device=-1):
                           lambda P, K, L: stat_shapes(model, P, K, L))
 
 
-def estep(model, data, draws, pairing="grid", device=-1, lib=None, return_status=False):
+def estep(model, data, draws, pairing="grid", device=-1, lib=None, return_status=False, schedule="auto", flags=0):
     """Expected sufficient statistics of every (series, draw) pair.
+
+    schedule: "lanes" (a lane, or a group of lanes above K = 8, walks each
+    series step by step), "scan" (the parallel scan over T, K <= 8: few pairs,
+    long series) or "auto" (resolve_schedule).  flags: HHMM_FLAG_SCAN_* for the
+    scan's chunk length (_abi.flag_scan_chunk_log2).
 
     Returns {name: array}: loglik (P,), n_1k (P, K), xi_ij (P, K, K) and c_kl
     (P, K, L) for hmm-multinom or w_k, s1_k, s2_k (P, K) for hmm.  A pair whose
@@ -71,7 +114,8 @@ def estep(model, data, draws, pairing="grid", device=-1, lib=None, return_status
     above 8."""
     lib = lib or load_library()
     pr, res, out = prepare(model, data, draws, pairing, device)
-    return _stats.call(lib, entry_name(pr.K), pr, res, out, return_status)
+    pr.req.flags = int(flags)
+    return _stats.call(lib, entry_name(pr.K, resolve_schedule(pr, schedule, lib)), pr, res, out, return_status)
 
 
 def pair_draw(pairing, P, S, N):

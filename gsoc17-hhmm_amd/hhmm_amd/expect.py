@@ -13,11 +13,22 @@ statistics are estep()'s, bit for bit.
 """
 from . import _stats
 from .api import load_library
+from .estep import resolve_schedule
 from .gibbs import MODELS, _request  # noqa: F401
 
 
-def expected_stats(model, data, draws, pairing="grid", device=-1, lib=None, return_status=False):
+def entry_name(schedule="lanes"):
+    """The library entry expected_stats() calls under a resolved schedule
+    (estep.resolve_schedule): "expected_stats", or "expected_stats_scan"."""
+    return "expected_stats_scan" if schedule == "scan" else "expected_stats"
+
+
+def expected_stats(model, data, draws, pairing="grid", device=-1, lib=None, return_status=False, schedule="auto",
+                   flags=0):
     """Expected sufficient statistics of every (series, draw) pair.
+
+    schedule ("auto", "lanes", "scan") and flags as for estep(): "scan" is the
+    parallel scan over T for few pairs and long series (hhmm_expected_stats_scan).
 
     draws as draw_stats() takes them ({p_1k, A_ij, phi_k}; hhmm-tayal2009:
     {p_11, A_row, phi_k}).  Returns {name: array}: loglik (P,), n_1k (P, K),
@@ -26,4 +37,6 @@ def expected_stats(model, data, draws, pairing="grid", device=-1, lib=None, retu
     exact zero.  A pair whose log-likelihood is -inf or NaN has NaN
     statistics."""
     lib = lib or load_library()
-    return _stats.call(lib, "expected_stats", *_request(model, data, draws, pairing, device), return_status)
+    pr, res, out = _request(model, data, draws, pairing, device)
+    pr.req.flags = int(flags)
+    return _stats.call(lib, entry_name(resolve_schedule(pr, schedule, lib)), pr, res, out, return_status)

@@ -32,7 +32,8 @@
  * models, K > 8, HHMM_DEVICE_SET and an emission table with L * ceil(K / 2) >
  * 80 (two tables of one wave do not fit a CU's LDS) answer HHMM_ERR_UNSUPPORTED.
  * The request is the hhmm_request of hhmm.h; outputs, ffbs_u, hat_rand and the
- * scan flags are ignored (the E-step is sequential in T per pair).
+ * scan flags are ignored (hhmm_estep is sequential in T per pair; for few, long
+ * series the hhmm_estep_scan entries below run the same E-step in parallel over T).
  * hmm and hmm-multinom at 8 < K <= 32 go to the hhmm_estep_large entries below.
  */
 #ifndef HHMM_ESTEP_H
@@ -110,6 +111,54 @@ hhmm_status hhmm_estep_large_workspace_size(const hhmm_request *req, size_t *byt
 hhmm_status hhmm_estep_large_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
                                     size_t workspace_bytes, void *stream);
 hhmm_status hhmm_estep_large(const hhmm_request *req, hhmm_estep_result *res);
+
+/* The E-step as a parallel scan over T, for one or a few long series (an EM
+ * fit of one long series from a handful of starts): three entries with the
+ * signatures of the first three, filling the same hhmm_estep_result with the
+ * same definitions, NaN rule and invalid-data rule as hhmm_estep.
+ *
+ *   Schedule  every series is cut into T-chunks of `cl` steps.  Phase 1 forms
+ *             each chunk's forward product, phase 2 turns the products into the
+ *             filter entering and the beta leaving every chunk (and loglik),
+ *             phase 3 gives one lane to one (pair, chunk) for the two sweeps of
+ *             hhmm_estep over that chunk, and a reduction adds the chunks'
+ *             statistics in chunk order.
+ *   Flags     HHMM_FLAG_SCAN_CHUNK_LOG2(n) sets cl = 2^n, rounded down to a
+ *             multiple of the checkpoint interval C (8 steps at K <= 4, else 4)
+ *             and at least C; left at 0 the library starts from 4 C and doubles
+ *             cl until P * ceil(T_max / cl) <= 262144.  These entries always
+ *             scan: HHMM_FLAG_SCAN_FORCE is implied, HHMM_FLAG_SCAN_OFF answers
+ *             HHMM_ERR_UNSUPPORTED, as does a request whose (pair, chunk) lanes
+ *             (a pair's chunks rounded up to a multiple of 64) reach 2^29.
+ *   Scope     hmm and hmm-multinom, 1 <= K <= 8, every pairing, ragged T.  K > 8
+ *             answers HHMM_ERR_UNSUPPORTED with a message that contains
+ *             "K = <value>" and names hhmm_estep_large; other models,
+ *             HHMM_DEVICE_SET and L * ceil(K / 2) > 80 as for hhmm_estep.
+ *   Accuracy  1e-9 relative to max(1, |value|) like hhmm_estep; not its bits
+ *             (the sums over t are associated by chunk).
+ *   Bits      no floating-point atomics: both entries and every run give the
+ *             same bits.
+ *   Workspace with nc = ceil(T_max / cl), ncw = nc rounded up to a multiple of
+ *             64 and ns = K + K^2 + K L (hmm: K + K^2 + 3 K) statistics, these
+ *             fp64 regions in this order, each rounded up to a multiple of 256
+ *             bytes, plus 256 bytes (the regions start at the first 256-byte
+ *             boundary of the workspace):
+ *               chunk products        nc K^2 P       their exponents    3 nc P
+ *               entering filters      nc K P         their log scales   nc P
+ *               leaving betas         nc K P         their log scales   nc P
+ *               in-chunk checkpoints  (cl / C) K P ncw
+ *               partials              P (ncw / 64) (ns + 5)
+ *               each pair's A         P K^2
+ * hhmm_estep_scan_plan (no device needed) returns the schedule hhmm_amd's
+ * schedule="auto" follows for this request: chunk_len = cl and n_chunks = nc of
+ * the scan when P < 4096 and T_max >= 8192 (or HHMM_FLAG_SCAN_FORCE is set)
+ * and the model and K are in the scope of hhmm_estep_scan or
+ * hhmm_expected_stats_scan; 0 and 0 for the sequential entry. */
+hhmm_status hhmm_estep_scan_workspace_size(const hhmm_request *req, size_t *bytes);
+hhmm_status hhmm_estep_scan_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+hhmm_status hhmm_estep_scan(const hhmm_request *req, hhmm_estep_result *res);
+hhmm_status hhmm_estep_scan_plan(const hhmm_request *req, int32_t *chunk_len, int32_t *n_chunks);
 
 #ifdef __cplusplus
 }

@@ -71,6 +71,18 @@ hhmm_status hhmm_expected_stats_device(const hhmm_request *req, hhmm_estep_resul
  * and synchronises. */
 hhmm_status hhmm_expected_stats(const hhmm_request *req, hhmm_estep_result *res);
 
+/* The expected statistics as a parallel scan over T (few pairs, long series):
+ * the schedule, flags, workspace, accuracy and bit rules of hhmm_estep_scan
+ * (hhmm_estep.h) with the scope, definitions, NaN rule and invalid-data rule of
+ * hhmm_expected_stats.  The backward boundary vectors of the scan come from the
+ * forward chunk products applied as column maps: the adjoint needs no products
+ * of its own.  K > 8 answers HHMM_ERR_UNSUPPORTED with "K = <value>" in the
+ * message, which names hhmm_estep_large (hmm and hmm-multinom only). */
+hhmm_status hhmm_expected_stats_scan_workspace_size(const hhmm_request *req, size_t *bytes);
+hhmm_status hhmm_expected_stats_scan_device(const hhmm_request *req, hhmm_estep_result *res, void *workspace,
+                                            size_t workspace_bytes, void *stream);
+hhmm_status hhmm_expected_stats_scan(const hhmm_request *req, hhmm_estep_result *res);
+
 #ifdef __cplusplus
 }
 #endif
